@@ -14,6 +14,16 @@ The second headline workload, firfilt_crcf h=64 (configs[0] shape, 2^28
 samples per GPU so the 4 GB working set is far above the 256 MB Infinity
 Cache), is timed the same way and reported under "firfilt_crcf_h64".
 
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up and times
+that headline leg only and prints one JSON line: the headline record.
+Everything else described below -- the firfilt leg, the sharded stream, the
+resamp / dotprod / fftfilt legs, the measured ceilings, the per-call legs and
+the CPU baselines -- runs only with `--full` (where the `--no-*` options
+still drop single legs).  `--dump-outputs DIR` writes what the headline
+leg's last timed step left in its output buffer to DIR/firpfbch2_y.npy
+(float32 [k, 2] = re, im; `_rank<r>` appended with several ranks; see
+dump_output() for the fixed sample taken of a large output).
+
 Multi-GPU: one process per GPU.  `--gpus N` without a launcher starts N
 child ranks itself (fresh interpreters, started before this process makes
 any GPU call); under torch.distributed.run the env's RANK / WORLD_SIZE are
@@ -38,7 +48,7 @@ independent stream (C = the box's CPU share, stated in `cores`), beside the
 one-core figure; bounded samples (~10 s + ~5 s).  The secondary legs carry
 their own one-core oracle rates (firfilt, resamp, fftfilt, dotprod n=64).
 
-Output: two JSON lines.  The first ("aux") holds the secondary records
+Output with --full: two JSON lines.  The first ("aux") holds the secondary records
 (per-call legs, dotprod legs, the measured ceilings' launch shapes, the CPU
 baseline detail); the LAST line is the headline record, kept short, with
 firfilt_crcf_h64 as its final key.  Measured ceilings: hand-written HIP copy /
@@ -97,7 +107,16 @@ def parse():
                    help="processes for the aggregate CPU baseline (0: the host CPU share, at most 16)")
     p.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "traffic.json"),
                    help="PMC-derived HBM bytes per launch (from a separate rocprofv3 --pmc run)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary legs (sharded stream, firfilt, resamp, dotprod, fftfilt), the "
+                        "measured ceilings, the per-call legs and the CPU baselines; without it only the "
+                        "headline firpfbch2 leg is set up, warmed up and timed")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the headline leg's outputs of its last step to DIR/*.npy")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def launch_ranks(n):
@@ -237,6 +256,33 @@ def time_steps(run_step, steps, warmup, world, stream, info=None):
     return wall, gpu_ms
 
 
+DUMP_HEAD = 1 << 16       # complex outputs kept from each end of a sampled dump
+DUMP_SAMPLE = 1 << 22     # complex outputs drawn in between (32 MB as float32 pairs)
+
+
+def dump_output(dirname, name, y):
+    """--dump-outputs: write the interleaved complex float32 device array `y`
+    (what the leg's last timed step left in the caller's output buffer) to
+    dirname/name.npy as float32 [k, 2].  An array of up to 2^22 + 2^17
+    complex outputs is written whole; a larger one is reduced to its first
+    and last 2^16 outputs plus 2^22 drawn by a fixed-seed generator, in index
+    order (about 35 MB), so two builds run with the same arguments write the
+    same positions.  The
+    inputs are seeded and the warm-up floor adds launches in fours, so the
+    filter state the last step starts from does not depend on how many
+    warm-up launches the floor took."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    yc = y.view(-1, 2)
+    nc = yc.shape[0]
+    if nc > 2 * DUMP_HEAD + DUMP_SAMPLE:
+        mid = np.random.default_rng(20240229).integers(DUMP_HEAD, nc - DUMP_HEAD, DUMP_SAMPLE, dtype=np.int64)
+        idx = np.concatenate([np.arange(DUMP_HEAD, dtype=np.int64), np.sort(mid),
+                              np.arange(nc - DUMP_HEAD, nc, dtype=np.int64)])
+        yc = yc[torch.from_numpy(idx).to(y.device)]
+    np.save(os.path.join(dirname, name + ".npy"), yc.cpu().numpy())
+
+
 def bench_firpfbch2(args, world, rank, stream):
     M, m = 1024, 4
     n = args.samples - args.samples % (M // 2)
@@ -252,6 +298,8 @@ def bench_firpfbch2(args, world, rank, stream):
     wi = {}
     wall, gpu_ms = time_steps(step, args.steps, args.warmup, world, stream, wi)
     res = {"n": n, "nblocks": nblocks, "wall": wall, "gpu_ms": gpu_ms, "warm": wi}
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, "firpfbch2_y" if world == 1 else "firpfbch2_y_rank%d" % rank, y)
     q.destroy()
     del x, y
     torch.cuda.empty_cache()
@@ -633,7 +681,7 @@ def main():
     tot_pfb = allreduce_sum(pfb["n"] * args.steps, world)
 
     shd = None
-    if not args.no_shard:
+    if args.full and not args.no_shard:
         shd = bench_firpfbch2_sharded(args, world, rank, stream)
         t_shd = allreduce_max(shd["wall"], world)
         g_shd = allreduce_max(shd["gpu_ms"], world)
@@ -641,14 +689,14 @@ def main():
         csum_shd = allreduce_sum_i64(shd["checksum"], world)
 
     fir = None
-    if not args.no_firfilt:
+    if args.full and not args.no_firfilt:
         fir = bench_firfilt(args, world, rank, stream)
         t_fir = allreduce_max(fir["wall"], world)
         g_fir = allreduce_max(fir["gpu_ms"], world)
         tot_fir = allreduce_sum(fir["n"] * args.steps, world)
 
     rs = None
-    if not args.no_resamp:
+    if args.full and not args.no_resamp:
         rs = bench_resamp(args, world, rank, stream)
         first_rs = allreduce_max(rs["first_ms"], world)
         t_rs = allreduce_max(rs["wall"], world)
@@ -656,19 +704,19 @@ def main():
         tot_rs = allreduce_sum(rs["n"] * args.steps, world)
 
     dp = ff = None
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         dp = bench_dotprod(args, world, rank, stream)
         ff = bench_fftfilt(args, world, rank, stream)
         dp_t = {n: (allreduce_max(r["wall"], world), allreduce_max(r["gpu_ms"], world)) for n, r in dp["runs"].items()}
         ff_t = (allreduce_max(ff["wall"], world), allreduce_max(ff["gpu_ms"], world))
 
-    ceil = measured_ceilings(stream) if rank == 0 and not args.no_ceilings else None
+    ceil = measured_ceilings(stream) if args.full and rank == 0 and not args.no_ceilings else None
     percall = percall_gpu = None
-    if rank == 0 and world == 1 and not args.no_percall:
+    if args.full and rank == 0 and world == 1 and not args.no_percall:
         percall = percall_baseline()
         percall_gpu = percall_baseline(force_gpu=True)
     cpu = cpu2 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.cpu_seconds, args.cpu_procs or cpu_share())
         cpu2 = cpu_baselines_secondary(args.cpu_seconds / 4)
 
@@ -722,7 +770,8 @@ def main():
                                    "runs": percall_gpu}
         if cpu is not None:
             aux["cpu_baseline_detail"] = cpu
-        print(json.dumps(aux), flush=True)
+        if args.full:
+            print(json.dumps(aux), flush=True)
 
         # ---- the headline line
         launch_ms = g_pfb / args.steps

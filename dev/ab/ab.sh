@@ -6,11 +6,12 @@
 set -o pipefail
 cd "$(dirname "$0")/../.."
 mkdir -p gpurun_out
-FLAGS=${AB_FLAGS:---no-extra --no-shard --no-percall --no-cpu-baseline}
+LOG=$(mktemp)
+FLAGS=${AB_FLAGS:---full --no-extra --no-shard --no-percall --no-cpu-baseline}
 for rep in 1 2; do
   for d in "$@"; do
-    LQ_LIB_PATH=$d/libliquid_mi355x.so timeout -k 10 300 python bench.py $FLAGS > gpurun_out/ab.log 2>&1 || { tail -20 gpurun_out/ab.log; exit 1; }
-    tail -1 gpurun_out/ab.log | python3 -c "
+    LQ_LIB_PATH=$d/libliquid_mi355x.so timeout -k 10 300 python bench.py $FLAGS > $LOG 2>&1 || { tail -20 $LOG; exit 1; }
+    tail -1 $LOG | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 out = {'pfb2': d['roofline']['launch_ms']}

@@ -4,9 +4,11 @@
   independent HIP objects, each warmed up on its shard's halo, must
   reproduce the single-stream HIP run bit for bit (firpfbch2.c:252-281: the
   block parity `flag` and the last 2mM inputs are the whole state).
-* bench.py --gpus 2 started without a launcher spawns its own ranks (here
+* bench.py --full --gpus 2 started without a launcher spawns its own ranks (here
   both on the one GPU, counters over gloo) and reports n_gpus 2 with the
   same sharded-stream checksum as --gpus 1.
+* bench.py without --full times the headline leg only and prints one JSON
+  line; --dump-outputs writes that leg's last outputs.
 * Fast-path guards: an output pointer that is only 8-byte aligned must
   still give correct results (the fast analyzer stores 16 bytes at a time).
 """
@@ -70,8 +72,8 @@ def test_firfilt_sharded_objects_bit_exact():
 
 
 def _bench(gpus):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1",
-           "--samples", str(1 << 20), "--shard-samples", str(1 << 21), "--no-firfilt", "--no-resamp",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(gpus), "--steps", "2",
+           "--warmup", "1", "--samples", str(1 << 20), "--shard-samples", str(1 << 21), "--no-firfilt", "--no-resamp",
            "--no-extra", "--no-cpu-baseline", "--no-percall", "--no-ceilings"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
@@ -90,6 +92,31 @@ def test_bench_spawns_ranks_and_sharded_checksum_is_invariant():
     s1, s2 = one["firpfbch2_sharded_stream"], two["firpfbch2_sharded_stream"]
     assert s1["owned_samples"] == s2["owned_samples"] == 1 << 21
     assert s1["output_checksum"] == s2["output_checksum"]
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """without --full: one JSON line, the headline record with none of the
+    secondary legs; --dump-outputs writes the last step's analyzer output
+    (2^20 input samples -> 2^21 complex outputs, small enough to be written whole)"""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--samples", str(1 << 20), "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, out.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["ms_per_step"] > 0 and d["value"] > 0
+    # value = samples of all timed steps / their wall time, ms_per_step = that wall time / steps
+    assert abs(d["value"] * d["ms_per_step"] * 1e3 - (1 << 20)) < 1e-6 * (1 << 20)
+    for leg in ("firpfbch2_sharded_stream", "firfilt_crcf_h64", "resamp_crcf_r1037", "fftfilt_crcf_h512",
+                "dotprod_cccf_frac", "cpu_baseline"):
+        assert leg not in d
+    assert sorted(os.listdir(tmp_path)) == ["firpfbch2_y.npy"]
+    y = np.load(os.path.join(tmp_path, "firpfbch2_y.npy"))
+    assert y.dtype == np.float32 and y.shape == (1 << 21, 2)
+    assert np.isfinite(y).all() and np.abs(y).max() > 0
 
 
 def test_firpfbch2_output_8byte_aligned():
