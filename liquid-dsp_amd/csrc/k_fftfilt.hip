@@ -36,34 +36,6 @@ constexpr int FF_STAUX = 2;      // store cache policy: non-temporal (default po
 __device__ __forceinline__ float2 to_c2(float a) { return make_float2(a, 0.f); }
 __device__ __forceinline__ float2 to_c2(float2 a) { return a; }
 
-// The guarded form (firfilt's long filters, see lqk_fftfilt_run): every wave
-// flags (flags[8 seg + wave]) whether its inputs of a segment hold a value
-// outside the transform's safe class; k_ff_repair then recomputes the outputs
-// of flagged segments as the exact direct convolution (firfilt.c:322-338's
-// dot product over the true taps, then the user scale), so Inf / NaN reach
-// the outputs the direct filter gives them to and no transform sum
-// overflows.  (An exact path inside the transform kernels cost their
-// register allocation 7-20 spilled VGPRs.)
-// Unsafe: Inf, NaN, |v| > 2^100, or a nonzero |v| < 2^-60 (whose products
-// with the twiddles would reach the denormal range).
-__device__ __forceinline__ unsigned ff_unsafe1(float v)
-{
-    const unsigned a = __float_as_uint(v) & 0x7fffffffu;
-    return (unsigned)(a - 0x21800000u) > (0x71800000u - 0x21800000u) ? (a != 0u) : 0u;
-}
-__device__ __forceinline__ unsigned ff_unsafe(float2 v) { return ff_unsafe1(v.x) | ff_unsafe1(v.y); }
-// this wave's verdict on segment seg (lane 0 stores it): eight slots per
-// segment (the repair kernel reads them as two 16-byte words), the other
-// four cleared
-__device__ __forceinline__ void ff_flag(unsigned *flags, long long seg, unsigned bad)
-{
-    const unsigned long long any = __ballot(bad);
-    if ((threadIdx.x & 63) == 0) {
-        flags[8 * seg + (threadIdx.x >> 6)] = any != 0ull;
-        flags[8 * seg + 4 + (threadIdx.x >> 6)] = 0u;
-    }
-}
-
 // Register form: 256 threads, thread t holds segment samples
 // t + 256 n; forward 4096-point FFT (fft4096_r16), x H, inverse, all with the
 // data in registers and two LDS transposes per transform (35 KB LDS, four
@@ -72,8 +44,7 @@ template <bool REAL>
 __global__ __launch_bounds__(NT, FF_WPE) void k_fftfilt_r16(int hm1, const float2 *__restrict__ H,
                                                     const void *__restrict__ hist, const void *__restrict__ xin,
                                                     long long n, void *__restrict__ yout, float sre, float sim,
-                                                    const float2 *__restrict__ tw, unsigned *__restrict__ flags,
-                                                    lqk_hist_job hj)
+                                                    const float2 *__restrict__ tw, lqk_hist_job hj)
 {
     __shared__ __attribute__((aligned(16))) float2 lds[FFT4096_LDS];
     if constexpr (REAL) lq_hist_job_run<float>(hj);   // the object's next history
@@ -130,12 +101,6 @@ __global__ __launch_bounds__(NT, FF_WPE) void k_fftfilt_r16(int hm1, const float
                 v[q] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rx, ox, 0, 0));
         }
     }
-    if (!REAL && flags) {   // (uniform) firfilt: flag segments with unsafe inputs for k_ff_repair
-        unsigned bad = 0;
-#pragma unroll
-        for (int q = 0; q < 16; q++) bad |= ff_unsafe(v[q]);
-        ff_flag(flags, seg, bad);
-    }
     fft4096_r16<+1>(v, lds, w16, t);
 #pragma unroll
     for (int k = 0; k < 16; k++) v[k] = unpk(pk_cmul(pk(v[k]), pk(hv[k])));
@@ -179,8 +144,7 @@ template <bool A16>
 __global__ __launch_bounds__(NT, 3) void k_fftfilt8k(int hd, int hm1, const float2 *__restrict__ H,
                                                     const void *__restrict__ hist, const void *__restrict__ xin,
                                                     long long n, void *__restrict__ yout, float sre, float sim,
-                                                    const float2 *__restrict__ tw, unsigned *__restrict__ flags,
-                                                    lqk_hist_job hj)
+                                                    const float2 *__restrict__ tw, lqk_hist_job hj)
 {
     __shared__ __attribute__((aligned(16))) float2 lds[FFT4096_LDS];
     lq_hist_job_run<float2>(hj);   // the object's next history
@@ -246,12 +210,6 @@ __global__ __launch_bounds__(NT, 3) void k_fftfilt8k(int hd, int hm1, const floa
                 vo[q] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rx, o + 8u, 0, 0));
             }
         }
-        if (flags) {   // (uniform) firfilt: flag segments with unsafe inputs for k_ff_repair
-            unsigned bad = 0;
-#pragma unroll
-            for (int q = 0; q < 16; q++) bad |= ff_unsafe(ve[q]) | ff_unsafe(vo[q]);
-            ff_flag(flags, seg, bad);
-        }
         __builtin_amdgcn_sched_barrier(0);
         fft4096_r16<+1>(ve, lds, w16, t);
         __builtin_amdgcn_sched_barrier(0);
@@ -301,41 +259,6 @@ __global__ __launch_bounds__(NT, 3) void k_fftfilt8k(int hd, int hm1, const floa
     }
 }
 
-// The exact outputs of every flagged segment (see ff_flag): segment seg's
-// outputs are stream samples seg L .. seg L + L - 1 (L new outputs per
-// segment), each the reference's dot product over the true taps (natural
-// order, hlen) and the user scale -- crcf: real scale per component
-// (firfilt.c:337, an Inf in one component stays out of the other); cccf: the
-// complex product.  Persistent grid; a segment's eight wave flags are two
-// 16-byte loads.
-__global__ __launch_bounds__(NT) void k_ff_repair(const unsigned *__restrict__ flags, long long nseg, int L,
-                                                  const float2 *__restrict__ x, const float2 *__restrict__ hist,
-                                                  int hm1, long long n, float2 *__restrict__ y,
-                                                  const float *__restrict__ h, int hlen, int cc, float sre, float sim)
-{
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    for (long long seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
-        const u32x4 f = *reinterpret_cast<const u32x4 *>(flags + 8 * seg);
-        const u32x4 f2 = *reinterpret_cast<const u32x4 *>(flags + 8 * seg + 4);
-        if (!(f.x | f.y | f.z | f.w | f2.x | f2.y | f2.z | f2.w)) continue;
-        for (long long s = seg * L + threadIdx.x; s < seg * L + L && s < n; s += NT) {
-            float2 acc = make_float2(0.f, 0.f);
-            for (int k = 0; k < hlen; k++) {
-                const long long u = s - k;
-                const float2 v = u >= 0 ? x[u] : (u >= -hm1 ? hist[hm1 + u] : make_float2(0.f, 0.f));
-                if (cc) {
-                    const float hr = h[2 * k], hi = h[2 * k + 1];
-                    acc = make_float2(fmaf(-hi, v.y, fmaf(hr, v.x, acc.x)), fmaf(hi, v.x, fmaf(hr, v.y, acc.y)));
-                } else {
-                    acc = make_float2(fmaf(h[k], v.x, acc.x), fmaf(h[k], v.y, acc.y));
-                }
-            }
-            y[s] = cc ? make_float2(acc.x * sre - acc.y * sim, acc.x * sim + acc.y * sre)
-                      : make_float2(acc.x * sre, acc.y * sre);
-        }
-    }
-}
-
 } // namespace
 
 // transform size for a filter: 4096-point segments up to 2049 taps; complex
@@ -354,24 +277,10 @@ extern "C" unsigned int lqk_fftfilt_nfft(int real_io, unsigned int hlen)
     return !real_io && hlen - 1 <= 4096 ? 8192 : 0;
 }
 
-// flag buffer bytes for a guarded call of n samples (per launch chunk: the
-// buffer is reused chunk after chunk on the stream)
-extern "C" size_t lqk_fftfilt_flag_bytes(unsigned int hlen, unsigned int nfft, unsigned long long n)
-{
-    const unsigned long long CHN = 1ull << 27, nc = n < CHN ? n : CHN;
-    const int hm1 = (int)hlen - 1;
-    const unsigned long long L = nfft == 8192 ? 8192 - ((hm1 + 1) & ~1) : NFFT - hm1;
-    return (size_t)((nc + L - 1) / L + 1) * 32;
-}
-
 extern "C" void lqk_fftfilt_run(int real_io, unsigned int hlen, unsigned int nfft, const void *H, const void *hist,
                                 const void *x, unsigned long long n, void *y, float scale_re, float scale_im,
-                                const float *hx, int guard, void *flags, const lqk_hist_job *job, void *stream)
+                                const lqk_hist_job *job, void *stream)
 {
-    if (guard && (real_io || !hx || !flags)) {
-        fprintf(stderr, "error: fftfilt: guarded form needs complex I/O, the taps and a flag buffer\n");
-        exit(1);
-    }
     if (n == 0) return;
     if (nfft != lqk_fftfilt_nfft(real_io, hlen) || nfft == 0) {
         fprintf(stderr, "error: fftfilt: filter length %u exceeds the GPU transform limit\n", hlen);
@@ -398,31 +307,17 @@ extern "C" void lqk_fftfilt_run(int real_io, unsigned int hlen, unsigned int nff
             const unsigned grid = (unsigned)(nsegc < 768 ? nsegc : 768);   // persistent, three resident per CU
             const bool a16 = (((uintptr_t)xc | (uintptr_t)yc) & 15) == 0;
             hipLaunchKernelGGL(a16 ? k_fftfilt8k<true> : k_fftfilt8k<false>, dim3(grid), dim3(NT), 0, st, hd, hm1,
-                               (const float2 *)H, hc, (const void *)xc, (long long)nc, yc, sre, sim, tw,
-                               guard ? (unsigned *)flags : nullptr, hj);
-            LQ_CHECK_LAUNCH();
-            if (guard)
-                hipLaunchKernelGGL(k_ff_repair, dim3(256), dim3(NT), 0, st, (const unsigned *)flags, nsegc, 8192 - hd,
-                                   (const float2 *)xc, (const float2 *)hc, hm1, (long long)nc, (float2 *)yc, hx,
-                                   (int)hlen, guard == 2, scale_re, scale_im);
+                               (const float2 *)H, hc, (const void *)xc, (long long)nc, yc, sre, sim, tw, hj);
         } else {
             const int L = NFFT - hm1;
             const long long nsegc = ((long long)nc + L - 1) / L;
             const unsigned grid = (unsigned)(nsegc < 4096 ? nsegc : 4096);   // persistent, four resident per CU
             if (real_io)
                 hipLaunchKernelGGL((k_fftfilt_r16<true>), dim3(grid), dim3(NT), 0, st, hm1, (const float2 *)H, hc,
-                                   (const void *)xc, (long long)nc, yc, sre, sim, tw, nullptr, hj);
+                                   (const void *)xc, (long long)nc, yc, sre, sim, tw, hj);
             else
-            {
                 hipLaunchKernelGGL((k_fftfilt_r16<false>), dim3(grid), dim3(NT), 0, st, hm1, (const float2 *)H, hc,
-                                   (const void *)xc, (long long)nc, yc, sre, sim, tw,
-                                   guard ? (unsigned *)flags : nullptr, hj);
-                LQ_CHECK_LAUNCH();
-                if (guard)
-                    hipLaunchKernelGGL(k_ff_repair, dim3(256), dim3(NT), 0, st, (const unsigned *)flags, nsegc, L,
-                                       (const float2 *)xc, (const float2 *)hc, hm1, (long long)nc, (float2 *)yc, hx,
-                                       (int)hlen, guard == 2, scale_re, scale_im);
-            }
+                                   (const void *)xc, (long long)nc, yc, sre, sim, tw, hj);
         }
         LQ_CHECK_LAUNCH();
     }

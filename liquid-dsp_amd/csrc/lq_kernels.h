@@ -183,15 +183,13 @@ void lqk_fft_batch(unsigned int n, int dir, const void *x, void *y, unsigned lon
  * taps, 8192 for complex I/O up to 4097 taps, 0: too long);
  * H = FFT_nfft(h zero padded) (unscaled, lqk_fftfilt_make_H); scale = the
  * user scale; hist = previous hlen-1 inputs.  x must not alias y.
- * guard (complex I/O only): 0 fftfilt; 1 / 2 firfilt crcf / cccf --
- * segments whose inputs hold Inf / NaN, |v| > 2^100 or nonzero |v| < 2^-60
- * are recomputed as the direct convolution over hx (the natural-order taps,
- * hlen); flags: device scratch of lqk_fftfilt_flag_bytes(). */
+ * A transform's rounding error scales with the loudest sample of a segment,
+ * not with the inputs each output sees: for fftfilt only (firfilt is held to
+ * the direct form's per-output bound, tests/fir_bound.py). */
 unsigned int lqk_fftfilt_nfft(int real_io, unsigned int hlen);
-size_t lqk_fftfilt_flag_bytes(unsigned int hlen, unsigned int nfft, unsigned long long n);
 void lqk_fftfilt_run(int real_io, unsigned int hlen, unsigned int nfft, const void *H, const void *hist,
                      const void *x, unsigned long long n, void *y, float scale_re, float scale_im,
-                     const float *hx, int guard, void *flags, const lqk_hist_job *job, void *stream);
+                     const lqk_hist_job *job, void *stream);
 void lqk_fftfilt_make_H(const void *h_dev, unsigned int hlen, int is_complex, unsigned int nfft, void *H,
                         void *stream);
 

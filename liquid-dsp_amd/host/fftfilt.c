@@ -138,7 +138,7 @@ static void lq_fftf_block_dev(lq_fftf *q, const void *dx, unsigned long long n, 
     void *hold = q->d_hist[q->cur], *hnew = q->d_hist[q->cur ^ 1];
     /* the transform kernel also writes the next history (no launch of its own) */
     const lqk_hist_job job = {hold, x, n, hnew, hm1};
-    lqk_fftfilt_run(q->kind == LQ_RRRF, q->h_len, q->nfft, q->d_H, hold, x, n, dy, q->sre, q->sim, NULL, 0, NULL,
+    lqk_fftfilt_run(q->kind == LQ_RRRF, q->h_len, q->nfft, q->d_H, hold, x, n, dy, q->sre, q->sim,
                     hm1 ? &job : NULL, q->ctx.stream);
     if (hm1) q->cur ^= 1;
 }

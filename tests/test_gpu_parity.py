@@ -185,9 +185,9 @@ def test_firfilt_crcf_matrix_core_path_long_stream(t, hlen):
     # three-term bf16 split is float32-accurate, not bf16-accurate).
     r = rng(100 + hlen)
     h = coefs(r, t, hlen)
-    # complex filters past 64 taps on blocks of >= 8192 samples take the
-    # 8192-point overlap-save path (k_fftfilt8k, guarded form); the 6000-sample
-    # first call keeps the matrix-core kernels of 65..256 taps covered
+    # every length and call size runs the direct kernels (firfilt has no
+    # transform form; tests/test_gpu_fir_bound.py): a short first call, a
+    # long one continuing it and an unaligned tail
     n0, n1, n2 = 6000, (3 << 20) + 12345, 777
     x = samples(r, t, n0 + n1 + n2)
     esz = x.itemsize
