@@ -456,6 +456,41 @@ LQMI_MSRESAMP_API(msresamp_crcf, liquid_float_complex)
 LQMI_MSRESAMP_API(msresamp_cccf, liquid_float_complex)
 
 /* ------------------------------------------------------------------------ */
+/* firhilbf (liquid.h:2097-2176): Hilbert transform filter, real <-> complex */
+/* ------------------------------------------------------------------------ */
+/* _m: filter semi-length (4m+1 taps, delay 2m+1), at least 2; _As: stop-band
+   attenuation [dB].  decim: 2 real in, 1 complex out per call; interp: 1
+   complex in, 2 real out; r2c: 1 real in, 1 complex out; c2r: the real part.
+   All modes share the object's two windows. */
+typedef struct firhilbf_s *firhilbf;
+firhilbf firhilbf_create(unsigned int _m, float _As);
+void firhilbf_destroy(firhilbf _q);
+void firhilbf_print(firhilbf _q);
+void firhilbf_reset(firhilbf _q);
+void firhilbf_r2c_execute(firhilbf _q, float _x, liquid_float_complex *_y);
+void firhilbf_c2r_execute(firhilbf _q, liquid_float_complex _x, float *_y);
+void firhilbf_decim_execute(firhilbf _q, float *_x, liquid_float_complex *_y);
+void firhilbf_decim_execute_block(firhilbf _q, float *_x, unsigned int _n, liquid_float_complex *_y);
+void firhilbf_interp_execute(firhilbf _q, liquid_float_complex _x, float *_y);
+void firhilbf_interp_execute_block(firhilbf _q, liquid_float_complex *_x, unsigned int _n, float *_y);
+/* extensions: _n consecutive r2c / c2r calls; device-pointer forms of the
+   four block calls (_n counts calls: decim outputs, interp / r2c / c2r
+   inputs).  In the _dev forms the input and output ranges must not overlap:
+   a workgroup reads inputs that another may already have overwritten. */
+void firhilbf_r2c_execute_block(firhilbf _q, float *_x, unsigned long long _n, liquid_float_complex *_y);
+void firhilbf_c2r_execute_block(firhilbf _q, liquid_float_complex *_x, unsigned long long _n, float *_y);
+void firhilbf_decim_execute_block_dev(firhilbf _q, const float *_dx, unsigned long long _n,
+                                      liquid_float_complex *_dy);
+void firhilbf_interp_execute_block_dev(firhilbf _q, const liquid_float_complex *_dx, unsigned long long _n,
+                                       float *_dy);
+void firhilbf_r2c_execute_block_dev(firhilbf _q, const float *_dx, unsigned long long _n,
+                                    liquid_float_complex *_dy);
+void firhilbf_c2r_execute_block_dev(firhilbf _q, const liquid_float_complex *_dx, unsigned long long _n,
+                                    float *_dy);
+void firhilbf_set_stream(firhilbf _q, void *_hip_stream);
+void firhilbf_synchronize(firhilbf _q);
+
+/* ------------------------------------------------------------------------ */
 /* fftfilt (liquid.h:2192-2240): rrrf, crcf, cccf                            */
 /* ------------------------------------------------------------------------ */
 #define LQMI_FFTFILT_API(FFTFILT, TO, TC, TI)                                                   \

@@ -320,6 +320,21 @@ void lqk_resamp2(int kind, int mode, unsigned int m, int t0, float scale, const 
                  const void *hist1, void *hist0_new, void *hist1_new, const void *x, unsigned long long n,
                  void *y0, void *y1, void *stream);
 
+/* ---------------------------------------------------------------- firhilbf (Hilbert transform)
+ * n calls of one firhilbf mode (src/filter/src/firhilb.c:168-301).  hist0/hist1 =
+ * the two windows of 2m floats (oldest first); the updated windows go to
+ * hist0_new/hist1_new (must not alias).  taps: the 2m quadrature taps
+ * hq[j] = h[4m-1-2j].  decim: x 2n floats, y n complex; interp: x n complex,
+ * y 2n floats; r2c: x n floats, y n complex, t0 the toggle before the first
+ * call.  x and y must not overlap.  LQK_FIRHILB_TILE: calls per workgroup. */
+enum { LQK_FH_DECIM = 0, LQK_FH_INTERP, LQK_FH_R2C };
+#define LQK_FIRHILB_TILE 1024
+#define LQK_FIRHILB_MAXM 2048   /* the tile's windows and the taps in 64 KB of LDS */
+void lqk_firhilb(int mode, unsigned int m, int t0, const void *taps, const void *hist0, const void *hist1,
+                 void *hist0_new, void *hist1_new, const void *x, unsigned long long n, void *y, void *stream);
+/* c2r: y[i] = Re x[i] */
+void lqk_firhilb_c2r(const void *x, unsigned long long n, void *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

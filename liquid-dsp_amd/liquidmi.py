@@ -248,6 +248,26 @@ def _declare(L):
             "firpfbch_%s_execute_block_dev" % t: (None, [vp, vp, ull, vp]),
             "firpfbch_%s_set_stream" % t: (None, [vp, vp]),
         })
+    sig.update({
+        "firhilbf_create": (vp, [u, f]),
+        "firhilbf_destroy": (None, [vp]),
+        "firhilbf_print": (None, [vp]),
+        "firhilbf_reset": (None, [vp]),
+        "firhilbf_r2c_execute": (None, [vp, f, vp]),
+        "firhilbf_c2r_execute": (None, [vp, cfloat, vp]),
+        "firhilbf_decim_execute": (None, [vp, vp, vp]),
+        "firhilbf_decim_execute_block": (None, [vp, vp, u, vp]),
+        "firhilbf_interp_execute": (None, [vp, cfloat, vp]),
+        "firhilbf_interp_execute_block": (None, [vp, vp, u, vp]),
+        "firhilbf_r2c_execute_block": (None, [vp, vp, ull, vp]),
+        "firhilbf_c2r_execute_block": (None, [vp, vp, ull, vp]),
+        "firhilbf_decim_execute_block_dev": (None, [vp, vp, ull, vp]),
+        "firhilbf_interp_execute_block_dev": (None, [vp, vp, ull, vp]),
+        "firhilbf_r2c_execute_block_dev": (None, [vp, vp, ull, vp]),
+        "firhilbf_c2r_execute_block_dev": (None, [vp, vp, ull, vp]),
+        "firhilbf_set_stream": (None, [vp, vp]),
+        "firhilbf_synchronize": (None, [vp]),
+    })
     for d in FIRDES_DESIGNS:
         sig["liquid_firdes_" + d] = (None, [u, u, f, f, vp])
     sig.update({
@@ -815,6 +835,84 @@ class Resamp2(_Obj):
               RESAMP2_DECIM: "_decim_execute"}[mode]
         self._fn(fn)(self.q, ptr(x), ptr(y))
         return y
+
+
+class FirHilb(_Obj):
+    """firhilbf: Hilbert transform filter, 2:1 decimator (real -> complex) and
+    interpolator (complex -> real); 4m+1 taps, delay 2m+1."""
+    prefix = "firhilbf"
+    TILE = 1024   # calls per workgroup of the block kernels (LQK_FIRHILB_TILE)
+
+    def __init__(self, m, As):
+        self.m = m
+        self.q = self._fn("_create")(m, As)
+
+    def reset(self):
+        self._fn("_reset")(self.q)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
+
+    def decim_block(self, x):
+        """len(x) // 2 decim calls: real x -> complex y"""
+        x = np.ascontiguousarray(x, np.float32)
+        y = np.zeros(len(x) // 2, np.complex64)
+        self._fn("_decim_execute_block")(self.q, ptr(x), len(y), ptr(y))
+        return y
+
+    def interp_block(self, x):
+        """len(x) interp calls: complex x -> 2 len(x) real y"""
+        x = np.ascontiguousarray(x, np.complex64)
+        y = np.zeros(2 * len(x), np.float32)
+        self._fn("_interp_execute_block")(self.q, ptr(x), len(x), ptr(y))
+        return y
+
+    def r2c_block(self, x):
+        x = np.ascontiguousarray(x, np.float32)
+        y = np.zeros(len(x), np.complex64)
+        self._fn("_r2c_execute_block")(self.q, ptr(x), len(x), ptr(y))
+        return y
+
+    def c2r_block(self, x):
+        x = np.ascontiguousarray(x, np.complex64)
+        y = np.zeros(len(x), np.float32)
+        self._fn("_c2r_execute_block")(self.q, ptr(x), len(x), ptr(y))
+        return y
+
+    def decim(self, x):
+        """one call of the original API: two real samples -> one complex"""
+        x = np.ascontiguousarray(x, np.float32)
+        y = np.zeros(1, np.complex64)
+        self._fn("_decim_execute")(self.q, ptr(x), ptr(y))
+        return y[0]
+
+    def interp(self, v):
+        y = np.zeros(2, np.float32)
+        self._fn("_interp_execute")(self.q, _by_value(v, CRCF), ptr(y))
+        return y
+
+    def r2c(self, v):
+        y = np.zeros(1, np.complex64)
+        self._fn("_r2c_execute")(self.q, float(v), ptr(y))
+        return y[0]
+
+    def c2r(self, v):
+        y = np.zeros(1, np.float32)
+        self._fn("_c2r_execute")(self.q, _by_value(v, CRCF), ptr(y))
+        return y[0]
+
+    # device pointers; n counts calls (input and output must not overlap)
+    def decim_block_dev(self, dx, n, dy):
+        self._fn("_decim_execute_block_dev")(self.q, dx, n, dy)
+
+    def interp_block_dev(self, dx, n, dy):
+        self._fn("_interp_execute_block_dev")(self.q, dx, n, dy)
+
+    def r2c_block_dev(self, dx, n, dy):
+        self._fn("_r2c_execute_block_dev")(self.q, dx, n, dy)
+
+    def c2r_block_dev(self, dx, n, dy):
+        self._fn("_c2r_execute_block_dev")(self.q, dx, n, dy)
 
 
 class MsResamp2(_Obj):

@@ -5,6 +5,7 @@ One JSON object per workload: kernel time per call from HIP events on the
 objects' stream (20 warm-up + 30 timed calls), samples/s and algorithmic
 GB/s (bytes stated per workload) as a fraction of the 8 TB/s spec.
     python tools/bench_widened.py > gpurun_out/widened.json
+    python tools/bench_widened.py --halfband      (the resamp2 / firhilbf / msresamp rows alone)
 """
 import json
 import os
@@ -62,8 +63,45 @@ def report(name, ms, units, unit_name, nbytes, note):
     sys.stdout.flush()
 
 
+def halfband_rows(L):
+    """resamp2 decim / interp (m = 12), the firhilbf rows next to them (same
+    structure, less arithmetic per byte), msresamp r = 0.3 / 3.3"""
+    n = 1 << 26
+    x = cbuf(n)
+    y = torch.empty(2 * 4 * n, device="cuda")
+    r2 = LQ.Resamp2(12, 0.0, 60.0)
+    r2.set_stream(S)
+    ms = timed(lambda: L.resamp2_crcf_execute_block_dev(r2.q, LQ.RESAMP2_DECIM, x.data_ptr(), n // 2,
+                                                         y.data_ptr(), None))
+    report("resamp2_crcf decim m=12", ms, n, "input samples", 8 * n + 4 * n, "8 B/input + 8 B/output")
+    ms = timed(lambda: L.resamp2_crcf_execute_block_dev(r2.q, LQ.RESAMP2_INTERP, x.data_ptr(), n,
+                                                         y.data_ptr(), None))
+    report("resamp2_crcf interp m=12", ms, n, "input samples", 8 * n + 16 * n, "8 B/input + 16 B/output")
+    # firhilbf: 2^26 real inputs -> 2^25 complex outputs; 2^25 complex inputs -> 2^26 real outputs
+    fh = LQ.FirHilb(12, 60.0)
+    fh.set_stream(S)
+    nc = n // 2
+    ms = timed(lambda: fh.decim_block_dev(x.data_ptr(), nc, y.data_ptr()))
+    report("firhilbf decim m=12", ms, n, "input samples", 16 * nc, "8 B in + 8 B out per output")
+    ms = timed(lambda: fh.interp_block_dev(x.data_ptr(), nc, y.data_ptr()))
+    report("firhilbf interp m=12", ms, nc, "input samples", 16 * nc, "8 B in + 8 B out per input")
+    fh.destroy()
+    for rate in (0.3, 3.3):
+        ms_ = LQ.MsResamp(rate, 60.0)
+        ms_.set_stream(S)
+        nin = n if rate < 1 else n // 4
+        nout = ms_.num_output(nin)
+        ms = timed(lambda: ms_.execute_block_dev(x.data_ptr(), nin, y.data_ptr()))
+        report("msresamp_crcf r=%g" % rate, ms, nin, "input samples", 8 * nin + 8 * nout,
+               "8 B/input + 8 B/output")
+        ms_.destroy()
+
+
 def main():
     L = LQ.lib()
+    if "--halfband" in sys.argv[1:]:   # only the half-band rows (resamp2, firhilbf, msresamp)
+        halfband_rows(L)
+        return
     # firfilt rrrf / cccf, h = 64
     n = 1 << 27
     for t, esz in (("rrrf", 4), ("cccf", 8)):
@@ -196,27 +234,7 @@ def main():
                "output samples", 8 * nin + 8 * nout, "8 B/input + 8 B/output")
         rs.destroy()
     del x, y
-    # resamp2 decim / interp (m = 12), msresamp r = 0.3 / 3.3
-    n = 1 << 26
-    x = cbuf(n)
-    y = torch.empty(2 * 4 * n, device="cuda")
-    r2 = LQ.Resamp2(12, 0.0, 60.0)
-    r2.set_stream(S)
-    ms = timed(lambda: L.resamp2_crcf_execute_block_dev(r2.q, LQ.RESAMP2_DECIM, x.data_ptr(), n // 2,
-                                                         y.data_ptr(), None))
-    report("resamp2_crcf decim m=12", ms, n, "input samples", 8 * n + 4 * n, "8 B/input + 8 B/output")
-    ms = timed(lambda: L.resamp2_crcf_execute_block_dev(r2.q, LQ.RESAMP2_INTERP, x.data_ptr(), n,
-                                                         y.data_ptr(), None))
-    report("resamp2_crcf interp m=12", ms, n, "input samples", 8 * n + 16 * n, "8 B/input + 16 B/output")
-    for rate in (0.3, 3.3):
-        ms_ = LQ.MsResamp(rate, 60.0)
-        ms_.set_stream(S)
-        nin = n if rate < 1 else n // 4
-        nout = ms_.num_output(nin)
-        ms = timed(lambda: ms_.execute_block_dev(x.data_ptr(), nin, y.data_ptr()))
-        report("msresamp_crcf r=%g" % rate, ms, nin, "input samples", 8 * nin + 8 * nout,
-               "8 B/input + 8 B/output")
-        ms_.destroy()
+    halfband_rows(L)
     # FFT API batches
     for N in (256, 512, 1024, 2048, 4096, 8192, 16384, 65536, 12345):
         B = (1 << 26) // N
