@@ -1,6 +1,6 @@
 // k_pfb2_fast.hip -- firpfbch2_crcf analyzer, M = 1024, fast path.
 //
-// Same closed form as csrc/k_channelizer.hip (reference
+// Same closed form as csrc/k_firpfbch2.hip (reference
 // src/multichannel/src/firpfbch2.c:244-282), restructured for CDNA4:
 //
 //  * View the input as rows of M = 1024 samples (row c = x[cM .. cM+M) in
@@ -58,16 +58,6 @@ __device__ __forceinline__ void lds_fence()
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Workgroup barrier for LDS hand-offs only: waits for this wave's LDS
-// operations, not for its global loads or stores (__syncthreads() would also
-// drain the prefetched rows and the output stores at every phase change).
-__device__ __forceinline__ void lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
 }
 
 struct Params {
@@ -266,7 +256,7 @@ __global__ __launch_bounds__(NT, 1) void k_pfb2_an1024(Params P, const float *__
             xb[s1 * BSTR + j] = dot(r, ta);
             xb[s2 * BSTR + j] = dot(r, tb);
         }
-        lds_barrier();
+        lq_lds_sync();
         // the next group's rows, issued after the barrier (before it: 0.635
         // -> 0.624 ms per 2^27 samples, r06c in profiles/r06_ab_experiments.txt)
         if (g + 1 < ge) fetch_group(g + 1, pf);
@@ -344,7 +334,7 @@ __global__ __launch_bounds__(NT, 1) void k_pfb2_an1024(Params P, const float *__
             }
         }
         slot0 = slot0 == 0 ? NBUF - 1 : slot0 - 1; // (16(g+1)) mod 17
-        lds_barrier();
+        lq_lds_sync();
     }
 }
 
@@ -520,11 +510,11 @@ __global__ __launch_bounds__(NT, 1) void k_pfb_an1024(const float2 *hist, const 
         // r06k / r06l); at p = 4 all sixteen, before it
         constexpr bool after = PF < 16;
         if (!after && g + 1 < ge) fetch_pf(g + 1, pf);
-        lds_barrier();
+        lq_lds_sync();
         if (after && g + 1 < ge) fetch_pf(g + 1, pf);
         const long long b = 16 * g + wave;
         if (b < nblk) fft1k_wave_store<+1>(xb + wave * BSTR, tw1, tw2, lane, Y + b * M);
-        lds_barrier();
+        lq_lds_sync();
     }
 }
 
@@ -552,7 +542,7 @@ __global__ __launch_bounds__(NT, 1) void k_pfb2_an1024_few(const float *__restri
     constexpr int HL = L * M - M2;
     const int j = tid;
     const int base = j < M2 ? (M2 - 1 - j) : (3 * M2 - 1 - j);
-    for (int b = 0; b < nb; b++) {   // firpfbch2.c:244-282 in closed form (k_channelizer.hip, k_pfb2_an)
+    for (int b = 0; b < nb; b++) {   // firpfbch2.c:244-282 in closed form (k_firpfbch2.hip, k_pfb2_an)
         const int bt = p0 + b;
         const int i = (j - (bt & 1) * M2) & (M - 1);
         const int c = j < M2 ? (bt >> 1) : ((bt - 1) >> 1);
@@ -681,7 +671,7 @@ __global__ __launch_bounds__(NT, 1) void k_pfb_syn1024(const float2 *__restrict_
         float2 v[16];
         if (b < nblk) load_block(b, v);
         if (b < nblk) fft1024_wave<-1>(v, zb + wave * BSTR, tw1, tw2, lane);
-        lds_barrier();
+        lq_lds_sync();
 #pragma unroll
         for (int r = 0; r < 16; r++) {
             const long long bb = 16 * g + r;
@@ -695,7 +685,7 @@ __global__ __launch_bounds__(NT, 1) void k_pfb_syn1024(const float2 *__restrict_
             }
             if (bb < nblk) y[bb * M + tid] = acc;
         }
-        lds_barrier();
+        lq_lds_sync();
     }
 }
 
@@ -779,7 +769,7 @@ __global__ __launch_bounds__(NT, 1) void k_pfb2_syn1024(const float2 *__restrict
             load_block(b, v);
             zform(v, zb + wave * BSTR);
         }
-        lds_barrier();
+        lq_lds_sync();
         load_taps();
 #pragma unroll
         for (int r = 0; r < 16; r++) {
@@ -798,7 +788,7 @@ __global__ __launch_bounds__(NT, 1) void k_pfb2_syn1024(const float2 *__restrict
                 y[bb * M2 + i] = make_float2(acc0.x + acc1.x, acc0.y + acc1.y);
             }
         }
-        lds_barrier();
+        lq_lds_sync();
     }
 }
 
@@ -820,14 +810,11 @@ extern "C" int lqk_firpfbch2_analyzer_fast(unsigned int Mch, unsigned int m, con
     if (nblocks <= 16) {   // a few blocks: one workgroup, no warm-up rows
         const lqk_hist_job hj = job ? *job : lqk_hist_job{nullptr, nullptr, 0ull, nullptr, 0u};
         const int p0 = (int)(B0 & 1);
-        if (m == 4)
-            hipLaunchKernelGGL((k_pfb2_an1024_few<8>), dim3(1), dim3(NT), 0, st, (const float *)hsub,
+        lq_switch<4, 8>(2 * m, [&](auto L) {
+            hipLaunchKernelGGL((k_pfb2_an1024_few<L>), dim3(1), dim3(NT), 0, st, (const float *)hsub,
                                (const float2 *)hist, (const float2 *)x, (int)nblocks, p0, (float2 *)Y, flag, seq, hj,
                                tw);
-        else
-            hipLaunchKernelGGL((k_pfb2_an1024_few<4>), dim3(1), dim3(NT), 0, st, (const float *)hsub,
-                               (const float2 *)hist, (const float2 *)x, (int)nblocks, p0, (float2 *)Y, flag, seq, hj,
-                               tw);
+        });
         LQ_CHECK_LAUNCH();
         return 1;
     }
@@ -858,14 +845,12 @@ extern "C" int lqk_firpfbch2_analyzer_fast(unsigned int Mch, unsigned int m, con
         P.gend = glast + 1;
         // paired 16-byte row loads need x and the history 16-byte aligned
         const bool pair = ((uintptr_t)P.x & 15) == 0 && ((uintptr_t)(P.hist + HL) & 15) == 0;
-        if (m == 4 && pair)
-            hipLaunchKernelGGL((k_pfb2_an1024<8, true>), dim3((unsigned)nwg), dim3(NT), 0, st, P, (const float *)hsub, tw);
-        else if (m == 4)
-            hipLaunchKernelGGL((k_pfb2_an1024<8, false>), dim3((unsigned)nwg), dim3(NT), 0, st, P, (const float *)hsub, tw);
-        else if (pair)
-            hipLaunchKernelGGL((k_pfb2_an1024<4, true>), dim3((unsigned)nwg), dim3(NT), 0, st, P, (const float *)hsub, tw);
-        else
-            hipLaunchKernelGGL((k_pfb2_an1024<4, false>), dim3((unsigned)nwg), dim3(NT), 0, st, P, (const float *)hsub, tw);
+        lq_switch<4, 8>(2 * m, [&](auto L) {
+            lq_switch<1, 0>(pair, [&](auto pr) {
+                hipLaunchKernelGGL((k_pfb2_an1024<L, pr != 0>), dim3((unsigned)nwg), dim3(NT), 0, st, P,
+                                   (const float *)hsub, tw);
+            });
+        });
         LQ_CHECK_LAUNCH();
     }
     return 1;
@@ -895,18 +880,12 @@ extern "C" int lqk_firpfbch_analyzer_fast(int ctaps, unsigned int Mch, unsigned 
         const unsigned nwg = (unsigned)((ngroups + gpw - 1) / gpw);
         const float2 *zero = (const float2 *)lqrt_zeros();
         const bool pair = ((uintptr_t)xs & 15) == 0 && ((uintptr_t)hs & 15) == 0;
-        if (p == 8 && pair)
-            hipLaunchKernelGGL((k_pfb_an1024<8, 8, true>), dim3(nwg), dim3(NT), 0, st, hs, xs, nb, (int)gpw,
-                               (const float *)hsub, tw, (float2 *)Y + ob * M, zero);
-        else if (p == 8)
-            hipLaunchKernelGGL((k_pfb_an1024<8, 8, false>), dim3(nwg), dim3(NT), 0, st, hs, xs, nb, (int)gpw,
-                               (const float *)hsub, tw, (float2 *)Y + ob * M, zero);
-        else if (pair)
-            hipLaunchKernelGGL((k_pfb_an1024<4, 16, true>), dim3(nwg), dim3(NT), 0, st, hs, xs, nb, (int)gpw,
-                               (const float *)hsub, tw, (float2 *)Y + ob * M, zero);
-        else
-            hipLaunchKernelGGL((k_pfb_an1024<4, 16, false>), dim3(nwg), dim3(NT), 0, st, hs, xs, nb, (int)gpw,
-                               (const float *)hsub, tw, (float2 *)Y + ob * M, zero);
+        lq_switch<4, 8>(p, [&](auto PP) {   // PF = 16 rows in flight at P = 4, 8 at P = 8
+            lq_switch<1, 0>(pair, [&](auto pr) {
+                hipLaunchKernelGGL((k_pfb_an1024<PP, PP == 8 ? 8 : 16, pr != 0>), dim3(nwg), dim3(NT), 0, st, hs, xs,
+                                   nb, (int)gpw, (const float *)hsub, tw, (float2 *)Y + ob * M, zero);
+            });
+        });
         LQ_CHECK_LAUNCH();
     }
     return 1;
@@ -925,12 +904,10 @@ extern "C" int lqk_firpfbch_analyzer_few(int ctaps, unsigned int Mch, unsigned i
     hipStream_t st = (hipStream_t)stream;
     const float2 *tw = (const float2 *)lqrt_twiddles();
     const lqk_hist_job hj = job ? *job : lqk_hist_job{nullptr, nullptr, 0ull, nullptr, 0u};
-    if (p == 8)
-        hipLaunchKernelGGL((k_pfb_an1024_few<8>), dim3(1), dim3(NT), 0, st, (const float *)hsub, (const float2 *)hist,
-                           (const float2 *)x, (int)nblocks, (float2 *)Y, flag, seq, hj, tw);
-    else
-        hipLaunchKernelGGL((k_pfb_an1024_few<4>), dim3(1), dim3(NT), 0, st, (const float *)hsub, (const float2 *)hist,
-                           (const float2 *)x, (int)nblocks, (float2 *)Y, flag, seq, hj, tw);
+    lq_switch<4, 8>(p, [&](auto PP) {
+        hipLaunchKernelGGL((k_pfb_an1024_few<PP>), dim3(1), dim3(NT), 0, st, (const float *)hsub,
+                           (const float2 *)hist, (const float2 *)x, (int)nblocks, (float2 *)Y, flag, seq, hj, tw);
+    });
     LQ_CHECK_LAUNCH();
     return 1;
 }
@@ -949,12 +926,10 @@ extern "C" int lqk_firpfbch_synthesizer_fast(int ctaps, unsigned int Mch, unsign
     long long gpw = (ngroups + 255) / 256;
     if (gpw < 2) gpw = 2;
     const unsigned nwg = (unsigned)((ngroups + gpw - 1) / gpw);
-    if (p == 8)
-        hipLaunchKernelGGL((k_pfb_syn1024<8>), dim3(nwg), dim3(NT), 0, st, (const float2 *)X, (long long)nblocks,
+    lq_switch<4, 8>(p, [&](auto PP) {
+        hipLaunchKernelGGL((k_pfb_syn1024<PP>), dim3(nwg), dim3(NT), 0, st, (const float2 *)X, (long long)nblocks,
                            (int)gpw, (const float *)hsub, (const float2 *)state, tw, (float2 *)y);
-    else
-        hipLaunchKernelGGL((k_pfb_syn1024<4>), dim3(nwg), dim3(NT), 0, st, (const float2 *)X, (long long)nblocks,
-                           (int)gpw, (const float *)hsub, (const float2 *)state, tw, (float2 *)y);
+    });
     LQ_CHECK_LAUNCH();
     // new state: Z of the last p-1 blocks (after the kernel has read the old one)
     lqk_fft_batch(M, -1, (const float2 *)X + (nblocks - (p - 1)) * M, state, p - 1, stream);
@@ -976,12 +951,10 @@ extern "C" int lqk_firpfbch2_synthesizer_fast(unsigned int Mch, unsigned int m, 
     long long gpw = (ngroups + 255) / 256;
     if (gpw < 2) gpw = 2;
     const unsigned nwg = (unsigned)((ngroups + gpw - 1) / gpw);
-    if (m == 4)
-        hipLaunchKernelGGL((k_pfb2_syn1024<8>), dim3(nwg), dim3(NT), 0, st, (const float2 *)X, (long long)nblocks,
+    lq_switch<4, 8>(2 * m, [&](auto L) {
+        hipLaunchKernelGGL((k_pfb2_syn1024<L>), dim3(nwg), dim3(NT), 0, st, (const float2 *)X, (long long)nblocks,
                            p0 & 1, (int)gpw, (const float *)hsub, (const float2 *)state, tw, (float2 *)Y);
-    else
-        hipLaunchKernelGGL((k_pfb2_syn1024<4>), dim3(nwg), dim3(NT), 0, st, (const float2 *)X, (long long)nblocks,
-                           p0 & 1, (int)gpw, (const float *)hsub, (const float2 *)state, tw, (float2 *)Y);
+    });
     LQ_CHECK_LAUNCH();
     // new state: z of the last 4m-1 blocks, formed as the reference does (IFFT, x 1/M, x M/2)
     lqk_fft_batch_scaled(M, -1, (const float2 *)X + (nblocks - HB) * M, state, HB, 1.0f / (float)M,

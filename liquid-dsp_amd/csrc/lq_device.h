@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 #include "lq_kernels.h"
 
@@ -14,6 +15,15 @@ void lq_check(hipError_t e, const char *what, const char *file, int line);
 #define LQ_CHECK_LAUNCH() lq_check(hipGetLastError(), "kernel launch", __FILE__, __LINE__)
 
 #define LQ_TW_N 4096
+
+// Host-side dispatch of a runtime value to a template argument: calls
+// f(std::integral_constant<int, V>{}) for the V in Vs... equal to v and
+// returns true; false (nothing called) if there is none.  The list is the
+// set of instantiations: lq_switch<2, 4>(L, [&](auto l) { launch<l>(..); })
+template <int... Vs, class F> bool lq_switch(int v, F &&f)
+{
+    return ((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
+}
 
 // Small-call completion (lq_runtime.hip): after this thread's result stores,
 // release them at system scope and raise the host's pinned flag word.  A
@@ -25,10 +35,12 @@ __device__ __forceinline__ void lq_signal(unsigned *flag, unsigned seq)
     __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// Workgroup barrier for LDS hand-offs: waits for this wave's LDS operations
-// only.  __syncthreads() also waits for every global load and store in
-// flight (vmcnt(0)), so a transform between a segment's stores and the next
-// segment's would hold the stores up at its first barrier.
+// Workgroup barrier for LDS hand-offs only: waits for this wave's LDS
+// operations, not for its global loads or stores.  __syncthreads() also
+// waits for every global load and store in flight (vmcnt(0)): it would drain
+// the prefetched rows and the output stores at every phase change, and a
+// transform between a segment's stores and the next segment's would hold the
+// stores up at its first barrier.
 __device__ __forceinline__ void lq_lds_sync()
 {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -141,7 +141,7 @@ int lqk_firpfbch_synthesizer_fast(int ctaps, unsigned int M, unsigned int p, con
 /* firpfbch2_crcf synthesizer M = 1024, m in {2, 4}, nblocks >= 4m-1; 0 = not handled */
 int lqk_firpfbch2_synthesizer_fast(unsigned int M, unsigned int m, const void *hsub, void *state, const void *X,
                                    unsigned long long nblocks, int p0, void *Y, void *stream);
-/* batched transforms with the two sequential output scales of fft_batch_scaled (k_channelizer.hip) */
+/* batched transforms with the two sequential output scales of lq_fft_batch_scaled (k_fft_batch.hip) */
 void lqk_fft_batch_scaled(unsigned int n, int dir, const void *x, void *y, unsigned long long batch, float s1,
                           float s2, void *stream);
 /* job (NULL: none) is done only when the call is handled (returns 1).
@@ -153,7 +153,7 @@ int lqk_firpfbch2_analyzer_fast(unsigned int M, unsigned int m, const void *hsub
                                 const lqk_hist_job *job, unsigned *flag, unsigned seq, void *stream);
 /* synthesizer: nblocks x M channel inputs -> nblocks x M/2 outputs.
  * state: the previous 4m-1 IFFT vectors (M each), zscratch (4m-1+nblocks)*M;
- * see csrc/k_channelizer.hip */
+ * see csrc/k_firpfbch2.hip */
 void lqk_firpfbch2_synthesizer(unsigned int M, unsigned int m, const void *hsub_syn,
                                void *state, void *zscratch, const void *X,
                                unsigned long long nblocks, int p0, void *Y, void *stream);

@@ -11,7 +11,7 @@
  *
  * GPU state: analyzer = last 2mM - M/2 input samples (ping-pong) and the
  * block parity (the reference's `flag`); synthesizer = last 4m-1 IFFT
- * vectors and the parity.  See csrc/k_channelizer.hip for the closed forms.
+ * vectors and the parity.  See csrc/k_firpfbch2.hip for the closed forms.
  */
 #include "lq_host.h"
 

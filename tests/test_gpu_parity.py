@@ -332,7 +332,10 @@ def test_fftfilt_long_stream_block_extension():
     assert G.nrm_err(y, ref) < NRM
 
 
-@pytest.mark.parametrize("M,m", [(2, 1), (8, 2), (12, 3), (64, 4), (256, 2), (1024, 4), (4096, 2)])
+# (4, 1) and the m = 9 cases: k_pfb2_an<M> for M = 4 and for every power of two
+# M >= 64 (m > 8 is past the polyphase pass's tap counts)
+@pytest.mark.parametrize("M,m", [(2, 1), (8, 2), (12, 3), (64, 4), (256, 2), (1024, 4), (4096, 2),
+                                 (4, 1), (64, 9), (128, 9), (256, 9), (512, 9), (1024, 9), (2048, 9), (4096, 9)])
 def test_firpfbch2_analyzer_vs_oracle(M, m):
     r = rng(M + m)
     nblocks = 64 if M <= 1024 else 8
@@ -375,7 +378,10 @@ def test_firpfbch2_m1024_few_block_calls(m, dev):
     assert G.nrm_err(np.concatenate(ys), o.execute_block(x)) < NRM
 
 
-@pytest.mark.parametrize("M,m", [(64, 4), (128, 1), (256, 4), (512, 3), (1024, 5), (2048, 4), (4096, 6), (256, 8)])
+# the last five reach k_pfb2_poly<L> for L = 2m = 2, 6, 14 and, at M = 8192
+# (no fused form, batched 8192-point transform), L = 4, 8
+@pytest.mark.parametrize("M,m", [(64, 4), (128, 1), (256, 4), (512, 3), (1024, 5), (2048, 4), (4096, 6), (256, 8),
+                                 (1024, 1), (1024, 3), (64, 7), (8192, 2), (8192, 4)])
 def test_firpfbch2_analyzer_polyphase_pass_vs_oracle(M, m):
     # power-of-two M other than the fused M=1024/m=4 path: polyphase pass
     # (column slices x row runs with a warm-up of 2m-1 rows each) + batched
@@ -554,7 +560,8 @@ def test_firpfbch2_perfect_reconstruction_gpu(M):
     assert np.max(np.abs(y[d:] - x[: n - d])) < 1e-3
 
 
-@pytest.mark.parametrize("M,m", [(8, 2), (64, 3), (1024, 4)])
+# (8, 4): k_pfb2_syn_out_run<8>; (8, 1): the per-element k_pfb2_syn_out
+@pytest.mark.parametrize("M,m", [(8, 2), (64, 3), (1024, 4), (8, 4), (8, 1)])
 def test_firpfbch2_synthesizer_vs_oracle(M, m):
     r = rng(M * 3)
     nb = 40
@@ -614,7 +621,13 @@ def test_firpfbch2_synthesizer_m1024_many_workgroups(m):
 
 
 @pytest.mark.parametrize("typ", [LQ.LIQUID_ANALYZER, LQ.LIQUID_SYNTHESIZER])
-@pytest.mark.parametrize("M,m", [(4, 2), (16, 3), (1024, 2), (6, 2)])
+# p = 2m.  M = 4: the run kernels' p = 2, 8, 10, 12, 14, 16; M = 256: the fused
+# M = 256 / 512 kernels' p = 2, 10, 12, 14; M = 64: the fused M = 64 / 128
+# kernels' p = 4, 10, 12, 14
+@pytest.mark.parametrize("M,m", [(4, 2), (16, 3), (1024, 2), (6, 2),
+                                 (4, 1), (4, 4), (4, 5), (4, 6), (4, 7), (4, 8),
+                                 (256, 1), (256, 5), (256, 6), (256, 7),
+                                 (64, 2), (64, 5), (64, 6), (64, 7)])
 def test_firpfbch_vs_oracle(typ, M, m):
     r = rng(M + 7 * typ)
     nb = 30
@@ -911,7 +924,8 @@ def test_firpfbch_m1024_fast_path_many_workgroups(typ, m):
 
 
 @pytest.mark.parametrize("typ", [LQ.LIQUID_ANALYZER, LQ.LIQUID_SYNTHESIZER])
-@pytest.mark.parametrize("M,p", [(8, 4), (64, 6), (6, 3)])
+# (4, 1): the run kernels' p = 1 (one tap per branch: explicit taps only)
+@pytest.mark.parametrize("M,p", [(8, 4), (64, 6), (6, 3), (4, 1)])
 def test_firpfbch_cccf_complex_taps(typ, M, p):
     # the channelizer is linear in its taps over the complex numbers:
     # A(hr + j hi) = A(hr) + j A(hi), so two real-tap oracle runs pin cccf
@@ -1379,7 +1393,8 @@ def test_fft_r2r_golden(case):
 
 @pytest.mark.parametrize("n", [32, 64, 128, 256, 512, 2048, 4096, 8192, 1 << 14, 1 << 15, 65536, 1 << 17, 1 << 20, 1000, 4099, 12345,
                                100003, 17,
-                               3 * 4096])
+                               3 * 4096,
+                               2, 4, 8, 16, 1024])   # k_fft_batch<N> and k_fft1024_batch through the plan API
 @pytest.mark.parametrize("direction", [+1, -1])
 def test_fft_sizes_vs_float64(n, direction):
     r = rng(n)
