@@ -491,6 +491,55 @@ void firhilbf_set_stream(firhilbf _q, void *_hip_stream);
 void firhilbf_synchronize(firhilbf _q);
 
 /* ------------------------------------------------------------------------ */
+/* iirfilt (liquid.h:2247-2378): rrrf, crcf, cccf                            */
+/* ------------------------------------------------------------------------ */
+/* Recursive filters from given coefficients: create (numerator / denominator,
+   divided by _a[0]; direct form II), create_sos (a cascade of second-order
+   sections, 3 coefficients each), and the ready-made DC blocker, PLL loop
+   filter, integrator and differentiator.  create_prototype and
+   create_lowpass (the Butterworth / Chebyshev / elliptic / Bessel designs)
+   are not part of this library yet and are deliberately not declared. */
+#define LQMI_IIRFILT_API(IIRFILT, TO, TC, TI)                                                   \
+    typedef struct IIRFILT##_s *IIRFILT;                                                        \
+    IIRFILT IIRFILT##_create(TC *_b, unsigned int _nb, TC *_a, unsigned int _na);               \
+    IIRFILT IIRFILT##_create_sos(TC *_B, TC *_A, unsigned int _nsos);                           \
+    IIRFILT IIRFILT##_create_integrator(void);                                                  \
+    IIRFILT IIRFILT##_create_differentiator(void);                                              \
+    IIRFILT IIRFILT##_create_dc_blocker(float _alpha);                                          \
+    IIRFILT IIRFILT##_create_pll(float _w, float _zeta, float _K);                              \
+    void IIRFILT##_destroy(IIRFILT _q);                                                         \
+    void IIRFILT##_print(IIRFILT _q);                                                           \
+    void IIRFILT##_reset(IIRFILT _q);                                                           \
+    void IIRFILT##_execute(IIRFILT _q, TI _x, TO *_y);                                          \
+    void IIRFILT##_execute_block(IIRFILT _q, TI *_x, unsigned int _n, TO *_y);                  \
+    unsigned int IIRFILT##_get_length(IIRFILT _q);                                              \
+    void IIRFILT##_freqresponse(IIRFILT _q, float _fc, liquid_float_complex *_H);               \
+    float IIRFILT##_groupdelay(IIRFILT _q, float _fc);                                          \
+    /* extensions: device pointers (_dy == _dx allowed); whether block calls run on the GPU   \
+       (SOS form up to 8 sections or at most 3 coefficients, no pole outside the unit         \
+       circle) or in the host loop */                                                          \
+    void IIRFILT##_execute_block_dev(IIRFILT _q, const TI *_dx, unsigned long long _n, TO *_dy); \
+    int IIRFILT##_device_eligible(IIRFILT _q);                                                  \
+    void IIRFILT##_set_stream(IIRFILT _q, void *_hip_stream);                                   \
+    void IIRFILT##_synchronize(IIRFILT _q);
+
+LQMI_IIRFILT_API(iirfilt_rrrf, float, float, float)
+LQMI_IIRFILT_API(iirfilt_crcf, liquid_float_complex, float, liquid_float_complex)
+LQMI_IIRFILT_API(iirfilt_cccf, liquid_float_complex, liquid_float_complex, liquid_float_complex)
+
+/* liquid.h:1621, 1829, 1848, 1864: the design helpers those constructors use */
+float iir_group_delay(float *_b, unsigned int _nb, float *_a, unsigned int _na, float _fc);
+void iirdes_dzpk2sosf(liquid_float_complex *_zd, liquid_float_complex *_pd, unsigned int _n,
+                      liquid_float_complex _kd, float *_B, float *_A);
+void iirdes_pll_active_lag(float _w, float _zeta, float _K, float *_b, float *_a);
+void iirdes_pll_active_PI(float _w, float _zeta, float _K, float *_b, float *_a);
+/* extension: samples per lane, per workgroup, and tiles per scan block of the
+   block-parallel kernels (csrc/k_iirfilt.hip) */
+unsigned int liquid_mi355x_iirfilt_run(void);
+unsigned int liquid_mi355x_iirfilt_tile(void);
+unsigned int liquid_mi355x_iirfilt_scan(void);
+
+/* ------------------------------------------------------------------------ */
 /* fftfilt (liquid.h:2192-2240): rrrf, crcf, cccf                            */
 /* ------------------------------------------------------------------------ */
 #define LQMI_FFTFILT_API(FFTFILT, TO, TC, TI)                                                   \

@@ -335,6 +335,32 @@ void lqk_firhilb(int mode, unsigned int m, int t0, const void *taps, const void 
 /* c2r: y[i] = Re x[i] */
 void lqk_firhilb_c2r(const void *x, unsigned long long n, void *y, void *stream);
 
+/* ---------------------------------------------------------------- iirfilt (recursive filters)
+ * n samples through a cascade of nsec <= LQK_IIRFILT_MAXSEC direct-form-II
+ * second-order sections (src/filter/src/iirfiltsos.c:167-184), block-parallel
+ * (k_iirfilt.hip).  kind 0 rrrf, 1 crcf, 2 cccf; samples S = float / float2,
+ * coefficients K = float (kind 0, 1) / float2.  With MS = lqk_iirfilt_maxsec(nsec)
+ * (nsec rounded up to a power of two) and PM = 2 MS:
+ *   coef    5 nsec K: b0, b1, b2, a1, a2 per section (a0 = 1)
+ *   ladder  LQK_IIRFILT_LEVELS matrices of PM x PM K, row-major: ladder[k] =
+ *           G^(2^k), G the map of the state over LQK_IIRFILT_RUN samples of
+ *           zero input
+ *   state   2 nsec S: v[1], v[2] of each section for the coming sample; read,
+ *           and left as after sample n-1
+ *   work    lqk_iirfilt_work_bytes(kind, nsec, n) bytes
+ * x == y allowed.  LQK_IIRFILT_RUN: consecutive samples per lane;
+ * LQK_IIRFILT_TILE: samples per workgroup; LQK_IIRFILT_SCAN: tiles per block
+ * of the cross-tile scan (more tiles than that: two scan levels). */
+#define LQK_IIRFILT_MAXSEC 8
+#define LQK_IIRFILT_RUN 16
+#define LQK_IIRFILT_TILE 4096
+#define LQK_IIRFILT_SCAN 256
+#define LQK_IIRFILT_LEVELS 23
+unsigned int lqk_iirfilt_maxsec(unsigned int nsec);
+size_t lqk_iirfilt_work_bytes(int kind, unsigned int nsec, unsigned long long n);
+void lqk_iirfilt(int kind, unsigned int nsec, const void *coef, const void *ladder, void *state, const void *x,
+                 unsigned long long n, void *y, void *work, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

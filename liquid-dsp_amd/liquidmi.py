@@ -268,6 +268,37 @@ def _declare(L):
         "firhilbf_set_stream": (None, [vp, vp]),
         "firhilbf_synchronize": (None, [vp]),
     })
+    for t in (RRRF, CRCF, CCCF):
+        ti = f if t == RRRF else cfloat
+        sig.update({
+            "iirfilt_%s_create" % t: (vp, [vp, u, vp, u]),
+            "iirfilt_%s_create_sos" % t: (vp, [vp, vp, u]),
+            "iirfilt_%s_create_integrator" % t: (vp, []),
+            "iirfilt_%s_create_differentiator" % t: (vp, []),
+            "iirfilt_%s_create_dc_blocker" % t: (vp, [f]),
+            "iirfilt_%s_create_pll" % t: (vp, [f, f, f]),
+            "iirfilt_%s_destroy" % t: (None, [vp]),
+            "iirfilt_%s_print" % t: (None, [vp]),
+            "iirfilt_%s_reset" % t: (None, [vp]),
+            "iirfilt_%s_execute" % t: (None, [vp, ti, vp]),
+            "iirfilt_%s_execute_block" % t: (None, [vp, vp, u, vp]),
+            "iirfilt_%s_execute_block_dev" % t: (None, [vp, vp, ull, vp]),
+            "iirfilt_%s_get_length" % t: (u, [vp]),
+            "iirfilt_%s_freqresponse" % t: (None, [vp, f, vp]),
+            "iirfilt_%s_groupdelay" % t: (f, [vp, f]),
+            "iirfilt_%s_device_eligible" % t: (i, [vp]),
+            "iirfilt_%s_set_stream" % t: (None, [vp, vp]),
+            "iirfilt_%s_synchronize" % t: (None, [vp]),
+        })
+    sig.update({
+        "iir_group_delay": (f, [vp, u, vp, u, f]),
+        "iirdes_dzpk2sosf": (None, [vp, vp, u, cfloat, vp, vp]),
+        "iirdes_pll_active_lag": (None, [f, f, f, vp, vp]),
+        "iirdes_pll_active_PI": (None, [f, f, f, vp, vp]),
+        "liquid_mi355x_iirfilt_run": (u, []),
+        "liquid_mi355x_iirfilt_tile": (u, []),
+        "liquid_mi355x_iirfilt_scan": (u, []),
+    })
     for d in FIRDES_DESIGNS:
         sig["liquid_firdes_" + d] = (None, [u, u, f, f, vp])
     sig.update({
@@ -913,6 +944,118 @@ class FirHilb(_Obj):
 
     def c2r_block_dev(self, dx, n, dy):
         self._fn("_c2r_execute_block_dev")(self.q, dx, n, dy)
+
+
+class _LibConst:
+    """a class attribute read from the library on first use"""
+
+    def __init__(self, fn):
+        self.fn = fn
+
+    def __get__(self, obj, owner):
+        return int(getattr(lib(), self.fn)())
+
+
+class IirFilt(_Obj):
+    """iirfilt_<t>: recursive filter.  IirFilt(t, b, a) is the numerator /
+    denominator form (create); the classmethods are the other constructors.
+    Block calls run on the GPU when device_eligible, else in the library's
+    host loop."""
+    family = "iirfilt_%s"
+    RUN = _LibConst("liquid_mi355x_iirfilt_run")     # consecutive samples per lane
+    TILE = _LibConst("liquid_mi355x_iirfilt_tile")   # samples per workgroup
+    SCAN = _LibConst("liquid_mi355x_iirfilt_scan")   # tiles per block of the cross-tile scan
+
+    def __init__(self, t, b, a):
+        self.t = t
+        self.prefix = self.family % t
+        self._b, self._a = _coefs(b, t), _coefs(a, t)
+        self.q = self._fn("_create")(ptr(self._b), len(self._b), ptr(self._a), len(self._a))
+
+    @classmethod
+    def sos(cls, t, B, A):
+        """create_sos: B, A of 3 coefficients per section"""
+        B, A = _coefs(B, t).ravel(), _coefs(A, t).ravel()
+        assert len(B) == len(A) and len(B) % 3 == 0
+        return cls.construct("_create_sos", (ptr(B), ptr(A), len(B) // 3), t=t, _b=B, _a=A)
+
+    @classmethod
+    def dc_blocker(cls, t, alpha):
+        return cls.construct("_create_dc_blocker", (alpha,), t=t)
+
+    @classmethod
+    def pll(cls, t, w, zeta, K):
+        return cls.construct("_create_pll", (w, zeta, K), t=t)
+
+    @classmethod
+    def integrator(cls, t):
+        return cls.construct("_create_integrator", (), t=t)
+
+    @classmethod
+    def differentiator(cls, t):
+        return cls.construct("_create_differentiator", (), t=t)
+
+    @property
+    def device_eligible(self):
+        return bool(self._fn("_device_eligible")(self.q))
+
+    def reset(self):
+        self._fn("_reset")(self.q)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
+
+    def get_length(self):
+        return int(self._fn("_get_length")(self.q))
+
+    def execute(self, v):
+        y = np.zeros(1, _out_dtype(self.t))
+        self._fn("_execute")(self.q, _by_value(v, self.t), ptr(y))
+        return y[0]
+
+    def execute_block(self, x):
+        x = _samples(x, self.t)
+        y = np.zeros(len(x), _out_dtype(self.t))
+        self._fn("_execute_block")(self.q, ptr(x), len(x), ptr(y))
+        return y
+
+    def execute_block_dev(self, dx, n, dy):
+        self._fn("_execute_block_dev")(self.q, dx, n, dy)
+
+    def freqresponse(self, fc):
+        H = np.zeros(1, np.complex64)
+        self._fn("_freqresponse")(self.q, fc, ptr(H))
+        return complex(H[0])
+
+    def groupdelay(self, fc):
+        return float(self._fn("_groupdelay")(self.q, fc))
+
+
+def iirdes_pll_active_lag(w, zeta, K):
+    b, a = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    lib().iirdes_pll_active_lag(w, zeta, K, ptr(b), ptr(a))
+    return b, a
+
+
+def iirdes_pll_active_PI(w, zeta, K):
+    b, a = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    lib().iirdes_pll_active_PI(w, zeta, K, ptr(b), ptr(a))
+    return b, a
+
+
+def iirdes_dzpk2sosf(z, p, k):
+    """zeros, poles, gain -> (B, A), 3 coefficients per section"""
+    z, p = np.ascontiguousarray(z, np.complex64), np.ascontiguousarray(p, np.complex64)
+    assert len(z) == len(p)
+    ns = (len(z) + 1) // 2
+    B, A = np.zeros(3 * ns, np.float32), np.zeros(3 * ns, np.float32)
+    lib().iirdes_dzpk2sosf(ptr(z), ptr(p), len(z), cfloat(float(np.real(k)), float(np.imag(k))), ptr(B), ptr(A))
+    return B, A
+
+
+def iir_group_delay(b, a, fc):
+    b, a = np.ascontiguousarray(b, np.float32), np.ascontiguousarray(a, np.float32)
+    return float(lib().iir_group_delay(ptr(b), len(b), ptr(a), len(a), fc))
 
 
 class MsResamp2(_Obj):

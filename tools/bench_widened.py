@@ -6,6 +6,7 @@ objects' stream (20 warm-up + 30 timed calls), samples/s and algorithmic
 GB/s (bytes stated per workload) as a fraction of the 8 TB/s spec.
     python tools/bench_widened.py > gpurun_out/widened.json
     python tools/bench_widened.py --halfband      (the resamp2 / firhilbf / msresamp rows alone)
+    python tools/bench_widened.py --iir           (the iirfilt rows alone)
 """
 import json
 import os
@@ -97,8 +98,57 @@ def halfband_rows(L):
         ms_.destroy()
 
 
+def iir_rows(L):
+    """iirfilt_crcf, 2^26 samples in place in device memory: the DC blocker (one
+    section) and a 4-section cascade (Butterworth order 8, fc 0.1, the sections
+    from scipy).  16 B/sample algorithmic; the kernels move 24 (the tile pass
+    reads x, the apply pass reads it again and writes y).  Then the device path
+    against the library's host loop at 2^20 samples, host pointers, wall clock."""
+    import time
+
+    import numpy as np
+    from scipy.signal import butter
+    n = 1 << 26
+    x = cbuf(n)
+    sos = butter(8, 0.2, output="sos").astype(np.float32)
+    filters = (("iirfilt_crcf dc_blocker alpha=0.01", lambda: LQ.IirFilt.dc_blocker("crcf", 0.01)),
+               ("iirfilt_crcf 4 sections (butter 8, fc 0.1)", lambda: LQ.IirFilt.sos("crcf", sos[:, :3], sos[:, 3:])))
+    for name, mk in filters:
+        q = mk()
+        assert q.device_eligible
+        q.set_stream(S)
+        ms = timed(lambda: q.execute_block_dev(x.data_ptr(), n, x.data_ptr()))
+        report(name, ms, n, "samples", 16 * n, "16 B/sample algorithmic (24 B/sample moved)")
+        q.destroy()
+    del x
+    nh = 1 << 20
+    xh = (np.random.default_rng(1).uniform(-0.5, 0.5, 2 * nh).astype(np.float32)).view(np.complex64)
+    # the host loop runs the objects that are not device-eligible: the same forms with one pole
+    # moved to radius 1 + 1e-7 (same arithmetic per sample; grows by 1.1 over 2^20 samples)
+    out = sos.copy()
+    out[3, 5] = np.float32(1.0000002)
+    hosts = (lambda: LQ.IirFilt("crcf", [1.0, -1.0], [1.0, -1.0000002]),
+             lambda: LQ.IirFilt.sos("crcf", out[:, :3], out[:, 3:]))
+    for (name, mk), mkh in zip(filters, hosts):
+        res = {}
+        for key, make, want in (("device_ms", mk, True), ("host_loop_ms", mkh, False)):
+            q = make()
+            assert q.device_eligible == want
+            q.execute_block(xh)
+            t0 = time.perf_counter()
+            for _ in range(3):
+                q.execute_block(xh)
+            res[key] = round((time.perf_counter() - t0) / 3 * 1e3, 3)
+            q.destroy()
+        print(json.dumps(dict({"workload": name + ", 2^20 samples, host pointers, wall clock"}, **res)))
+        sys.stdout.flush()
+
+
 def main():
     L = LQ.lib()
+    if "--iir" in sys.argv[1:]:
+        iir_rows(L)
+        return
     if "--halfband" in sys.argv[1:]:   # only the half-band rows (resamp2, firhilbf, msresamp)
         halfband_rows(L)
         return
@@ -235,6 +285,7 @@ def main():
         rs.destroy()
     del x, y
     halfband_rows(L)
+    iir_rows(L)
     # FFT API batches
     for N in (256, 512, 1024, 2048, 4096, 8192, 16384, 65536, 12345):
         B = (1 << 26) // N
