@@ -23,8 +23,6 @@
 
 #include "lq_host.h"
 
-static const char *lq_ext[] = {"rrrf", "crcf", "cccf"};
-
 typedef struct {
     int kind;
     size_t esz, csz;
@@ -33,26 +31,24 @@ typedef struct {
     float *h;
     float *hg;          /* reversed, expanded for the host path (lq_host_taps) */
     void *d_h, *d_H;
-    void *d_hist[2];    /* previous h_len-1 inputs */
-    int cur;
+    lq_hist hist;       /* previous h_len-1 inputs; mirrored for the small-call mode */
     float sre, sim;     /* user scale s */
     lq_firfilt *direct; /* h_len - 1 > NFFT/2: direct convolution */
-    lq_mirror hm;       /* host copy of the history (small-call mode) */
     lq_ctx ctx;
     lq_devbuf xbuf, ybuf, cbuf;
 } lq_fftf;
 
 static lq_fftf *lq_fftf_create(int kind, const float *h, unsigned int h_len, unsigned int n)
 {
-    if (h_len == 0) LQ_FAIL("error: fftfilt_%s_create(), filter length must be greater than zero\n", lq_ext[kind]);
+    if (h_len == 0) LQ_FAIL("error: fftfilt_%s_create(), filter length must be greater than zero\n", lq_ext(kind));
     if (n < h_len - 1)
-        LQ_FAIL("error: fftfilt_%s_create(), block length must be greater than _h_len-1 (%u)\n", lq_ext[kind],
+        LQ_FAIL("error: fftfilt_%s_create(), block length must be greater than _h_len-1 (%u)\n", lq_ext(kind),
                 h_len - 1);
     lqrt_require_device("fftfilt_create");
     lq_fftf *q = (lq_fftf *)lq_xmalloc(sizeof(*q));
     q->kind = kind;
-    q->esz = kind == LQ_RRRF ? 4 : 8;
-    q->csz = kind == LQ_CCCF ? 8 : 4;
+    q->esz = lq_esz(kind);
+    q->csz = lq_csz(kind);
     q->h_len = h_len;
     q->n = n;
     q->h = (float *)lq_xmalloc(h_len * q->csz);
@@ -62,9 +58,7 @@ static lq_fftf *lq_fftf_create(int kind, const float *h, unsigned int h_len, uns
     q->d_h = lqrt_malloc(h_len * q->csz);
     q->nfft = lqk_fftfilt_nfft(kind == LQ_RRRF, h_len);
     q->d_H = lqrt_malloc((size_t)(q->nfft ? q->nfft : 1) * 8);
-    q->d_hist[0] = lqrt_malloc((size_t)h_len * q->esz);
-    q->d_hist[1] = lqrt_malloc((size_t)h_len * q->esz);
-    lq_mirror_init(&q->hm, h_len - 1, q->esz);
+    lq_hist_init(&q->hist, h_len - 1, q->esz, LQ_HIST_MIRROR);
     lqrt_h2d(q->d_h, q->h, h_len * q->csz, q->ctx.stream);
     if (q->nfft == 0) {
         static const char *who[] = {"fftfilt_rrrf", "fftfilt_crcf", "fftfilt_cccf"};
@@ -76,7 +70,6 @@ static lq_fftf *lq_fftf_create(int kind, const float *h, unsigned int h_len, uns
     lqrt_sync(q->ctx.stream);
     q->sre = 1.0f;
     q->sim = 0.0f;
-    q->cur = 0;
     return q;
 }
 
@@ -86,9 +79,7 @@ static void lq_fftf_destroy(lq_fftf *q)
     if (q->direct) lq_firfilt_destroy(q->direct);
     lqrt_free(q->d_h);
     lqrt_free(q->d_H);
-    lqrt_free(q->d_hist[0]);
-    lqrt_free(q->d_hist[1]);
-    lq_mirror_free(&q->hm);
+    lq_hist_free(&q->hist);
     lq_devbuf_free(&q->xbuf);
     lq_devbuf_free(&q->ybuf);
     lq_devbuf_free(&q->cbuf);
@@ -100,16 +91,13 @@ static void lq_fftf_destroy(lq_fftf *q)
 
 static void lq_fftf_reset(lq_fftf *q)
 {
-    lqrt_memset(q->d_hist[0], (size_t)q->h_len * q->esz, q->ctx.stream);
-    lqrt_memset(q->d_hist[1], (size_t)q->h_len * q->esz, q->ctx.stream);
-    lqrt_sync(q->ctx.stream);
-    lq_mirror_zero(&q->hm);
+    lq_hist_zero(&q->hist, q->ctx.stream);
     if (q->direct) lq_firfilt_reset(q->direct);
 }
 
 static void lq_fftf_print(lq_fftf *q)
 {
-    printf("fftfilt_%s: [h_len=%u, n=%u]\n", lq_ext[q->kind], q->h_len, q->n);
+    printf("fftfilt_%s: [h_len=%u, n=%u]\n", lq_ext(q->kind), q->h_len, q->n);
     for (unsigned int i = 0; i < q->h_len; i++) {
         const unsigned int k = q->h_len - i - 1;
         if (q->kind == LQ_CCCF) printf("  h(%3u) = %12.8f + j*%12.8f\n", i + 1, q->h[2 * k], q->h[2 * k + 1]);
@@ -126,8 +114,7 @@ static void lq_fftf_block_dev(lq_fftf *q, const void *dx, unsigned long long n, 
         lq_firfilt_execute_block_dev(q->direct, dx, n, dy);
         return;
     }
-    lq_mirror_need_dev(&q->hm, q->d_hist[q->cur], q->ctx.stream);
-    q->hm.host_valid = 0;
+    void *hold = lq_hist_dev(&q->hist, q->ctx.stream), *hnew = lq_hist_next(&q->hist);
     const void *x = dx;
     if (dx == dy) { /* kernel segments read overlapping halos */
         void *c = lq_devbuf_get(&q->cbuf, (size_t)n * q->esz);
@@ -135,12 +122,11 @@ static void lq_fftf_block_dev(lq_fftf *q, const void *dx, unsigned long long n, 
         x = c;
     }
     const unsigned int hm1 = q->h_len - 1;
-    void *hold = q->d_hist[q->cur], *hnew = q->d_hist[q->cur ^ 1];
     /* the transform kernel also writes the next history (no launch of its own) */
     const lqk_hist_job job = {hold, x, n, hnew, hm1};
     lqk_fftfilt_run(q->kind == LQ_RRRF, q->h_len, q->nfft, q->d_H, hold, x, n, dy, q->sre, q->sim,
                     hm1 ? &job : NULL, q->ctx.stream);
-    if (hm1) q->cur ^= 1;
+    lq_hist_flip(&q->hist);
 }
 
 /* small-call mode: one short call (n h_len <= LQ_FFTF_HOST_MACS) on the host
@@ -150,25 +136,14 @@ static void lq_fftf_block_dev(lq_fftf *q, const void *dx, unsigned long long n, 
 #define LQ_FFTF_HOST_MACS 65536u
 static void lq_fftf_exec_host(lq_fftf *q, const void *x, unsigned int n, void *y)
 {
-    lq_mirror_need_host(&q->hm, q->d_hist[q->cur], q->ctx.stream);
-    lq_mirror_append(&q->hm, x, n);
-    const unsigned char *w = lq_mirror_ptr(&q->hm);
+    const unsigned char *w = lq_hist_append(&q->hist, x, n, q->ctx.stream);
     for (unsigned int t = 0; t < n; t++) {
         float *yt = (float *)((unsigned char *)y + (size_t)t * q->esz);
         /* window samples t .. t + h_len - 1 (oldest first) against the reversed taps */
         lq_host_tdot(q->kind, q->hg, w + (size_t)t * q->esz, q->h_len, yt);
-        if (q->kind == LQ_RRRF) {
-            yt[0] *= q->sre;
-        } else if (q->kind == LQ_CRCF) {   /* real scale per component */
-            yt[0] *= q->sre;
-            yt[1] *= q->sre;
-        } else {                           /* complex scale */
-            const float a = yt[0], b = yt[1];
-            yt[0] = a * q->sre - b * q->sim;
-            yt[1] = a * q->sim + b * q->sre;
-        }
+        lq_host_scale(q->kind, q->sre, q->sim, yt);
     }
-    lq_mirror_commit(&q->hm, n);
+    lq_hist_commit(&q->hist, n);
 }
 
 /* single: the call is fftfilt_*_execute (the reference's one n-sample block);

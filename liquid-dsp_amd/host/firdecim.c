@@ -18,7 +18,36 @@
 
 #include "lq_host.h"
 
-static const char *lq_ext[] = {"rrrf", "crcf", "cccf"};
+/* the designs behind both objects' create_kaiser (firdecim.c:88-122: 2Mm+1
+ * Kaiser taps at fc = 0.5/M, of which the first 2Mm are used) and
+ * create_prototype (firdecim.c:126-160, firinterp.c:124-158: 2Mm+1 taps from
+ * liquid_firdes_prototype); `what` is the factor's name in the messages */
+static float *lq_mrate_kaiser(const char *who, const char *what, unsigned int M, unsigned int m, float As,
+                              unsigned int *n)
+{
+    if (M < 2) LQ_FAIL("error: %s_create_kaiser(), %s factor must be greater than 1\n", who, what);
+    if (m == 0) LQ_FAIL("error: %s_create_kaiser(), filter delay must be greater than 0\n", who);
+    if (As < 0.0f) LQ_FAIL("error: %s_create_kaiser(), stop-band attenuation must be positive\n", who);
+    *n = 2 * M * m + 1;
+    float *hf = (float *)lq_xmalloc(*n * sizeof(float));
+    lq_firdes_kaiser(*n, 0.5f / (float)M, As, 0.0f, hf);
+    return hf;
+}
+
+static float *lq_mrate_prototype(const char *who, const char *what, int type, unsigned int M, unsigned int m,
+                                 float beta, float dt, unsigned int *n)
+{
+    if (M < 2) LQ_FAIL("error: %s_create_prototype(), %s factor must be greater than 1\n", who, what);
+    if (m == 0) LQ_FAIL("error: %s_create_prototype(), filter delay must be greater than 0\n", who);
+    if (beta < 0.0f || beta > 1.0f)
+        LQ_FAIL("error: %s_create_prototype(), filter excess bandwidth factor must be in [0,1]\n", who);
+    if (dt < -1.0f || dt > 1.0f)
+        LQ_FAIL("error: %s_create_prototype(), filter fractional sample delay must be in [-1,1]\n", who);
+    *n = 2 * M * m + 1;
+    float *hf = (float *)lq_xmalloc(*n * sizeof(float));
+    liquid_firdes_prototype((liquid_firfilt_type)type, M, m, beta, dt, hf);
+    return hf;
+}
 
 /* ================================================================ firdecim */
 
@@ -32,22 +61,20 @@ typedef struct {
     void *d_hpad;
     void *d_hq;        /* M x QC phase-major taps for the phase-layout kernel */
     unsigned int QC;
-    void *d_hist[2];   /* last hlen-1 inputs */
-    int cur;
-    lq_mirror hm;      /* host copy of the history (small-call mode) */
+    lq_hist hist;      /* last hlen-1 inputs; mirrored for the small-call mode */
     lq_ctx ctx;
     lq_devbuf xbuf, ybuf;
 } lq_decim;
 
 static lq_decim *lq_decim_create(int kind, unsigned int M, const float *h, unsigned int hlen)
 {
-    if (hlen == 0) LQ_FAIL("error: decim_%s_create(), filter length must be greater than zero\n", lq_ext[kind]);
-    if (M == 0) LQ_FAIL("error: decim_%s_create(), decimation factor must be greater than zero\n", lq_ext[kind]);
+    if (hlen == 0) LQ_FAIL("error: decim_%s_create(), filter length must be greater than zero\n", lq_ext(kind));
+    if (M == 0) LQ_FAIL("error: decim_%s_create(), decimation factor must be greater than zero\n", lq_ext(kind));
     lqrt_require_device("firdecim_create");
     lq_decim *q = (lq_decim *)lq_xmalloc(sizeof(*q));
     q->kind = kind;
-    q->esz = kind == LQ_RRRF ? 4 : 8;
-    q->csz = kind == LQ_CCCF ? 8 : 4;
+    q->esz = lq_esz(kind);
+    q->csz = lq_csz(kind);
     q->M = M;
     q->hlen = hlen;
     q->h = (float *)lq_xmalloc(hlen * q->csz);
@@ -65,8 +92,7 @@ static lq_decim *lq_decim_create(int kind, unsigned int M, const float *h, unsig
         memcpy(hq + ((size_t)(k % M) * q->QC + k / M) * cf, q->h + (size_t)k * cf, q->csz);
     q->d_hq = lqrt_malloc(nq * q->csz);
     lqrt_h2d(q->d_hq, hq, nq * q->csz, q->ctx.stream);
-    q->d_hist[0] = lqrt_malloc((size_t)hlen * q->esz);
-    q->d_hist[1] = lqrt_malloc((size_t)hlen * q->esz);
+    lq_hist_init(&q->hist, hlen - 1, q->esz, LQ_HIST_MIRROR);
     lqrt_sync(q->ctx.stream);
     free(hq);
     q->d.kind = kind;
@@ -76,20 +102,7 @@ static lq_decim *lq_decim_create(int kind, unsigned int M, const float *h, unsig
     q->d.hpad = q->d_hpad;
     q->d.scale_re = 1.0f;
     q->d.scale_im = 0.0f;
-    lq_mirror_init(&q->hm, hlen - 1, q->esz);
     return q;
-}
-
-/* firdecim.c:88-122: 2Mm+1 Kaiser taps at fc = 0.5/M, first 2Mm used */
-static float *lq_decim_kaiser(const char *who, unsigned int M, unsigned int m, float As, unsigned int *n)
-{
-    if (M < 2) LQ_FAIL("error: %s_create_kaiser(), decim factor must be greater than 1\n", who);
-    if (m == 0) LQ_FAIL("error: %s_create_kaiser(), filter delay must be greater than 0\n", who);
-    if (As < 0.0f) LQ_FAIL("error: %s_create_kaiser(), stop-band attenuation must be positive\n", who);
-    *n = 2 * M * m + 1;
-    float *hf = (float *)lq_xmalloc(*n * sizeof(float));
-    lq_firdes_kaiser(*n, 0.5f / (float)M, As, 0.0f, hf);
-    return hf;
 }
 
 static void lq_decim_destroy(lq_decim *q)
@@ -97,12 +110,10 @@ static void lq_decim_destroy(lq_decim *q)
     lqrt_sync(q->ctx.stream);
     lqrt_free(q->d_hpad);
     lqrt_free(q->d_hq);
-    lqrt_free(q->d_hist[0]);
-    lqrt_free(q->d_hist[1]);
+    lq_hist_free(&q->hist);
     lq_devbuf_free(&q->xbuf);
     lq_devbuf_free(&q->ybuf);
     lq_ctx_free(&q->ctx);
-    lq_mirror_free(&q->hm);
     free(q->h);
     free(q->hg);
     free(q);
@@ -117,36 +128,25 @@ static void lq_decim_print(lq_decim *q)
     }
 }
 
-static void lq_decim_clear(lq_decim *q)
-{
-    lqrt_memset(q->d_hist[0], (size_t)q->hlen * q->esz, q->ctx.stream);
-    lqrt_memset(q->d_hist[1], (size_t)q->hlen * q->esz, q->ctx.stream);
-    lqrt_sync(q->ctx.stream);
-    lq_mirror_zero(&q->hm);
-}
+static void lq_decim_clear(lq_decim *q) { lq_hist_zero(&q->hist, q->ctx.stream); }
 
 static void lq_decim_block_dev(lq_decim *q, const void *dx, unsigned long long nout, void *dy)
 {
     if (nout == 0) return;
-    lq_mirror_need_dev(&q->hm, q->d_hist[q->cur], q->ctx.stream);
-    q->hm.host_valid = 0;
-    void *hold = q->d_hist[q->cur], *hnew = q->d_hist[q->cur ^ 1];
+    void *hold = lq_hist_dev(&q->hist, q->ctx.stream), *hnew = lq_hist_next(&q->hist);
     if (lqk_firdecim_ph(q->kind, q->M, q->QC, q->d_hq, q->hlen - 1, hold, dx, nout, dy, q->ctx.stream) != 0)
         lqk_firdecim(&q->d, q->M, hold, dx, nout, dy, q->ctx.stream);
-    if (q->hlen > 1) {
-        lqk_window_append(q->kind != LQ_RRRF, hold, q->hlen - 1, dx, nout * q->M, hnew, q->ctx.stream);
-        q->cur ^= 1;
-    }
+    if (q->hlen > 1) lqk_window_append(q->kind != LQ_RRRF, hold, q->hlen - 1, dx, nout * q->M, hnew, q->ctx.stream);
+    lq_hist_flip(&q->hist);
 }
 
 /* small-call mode: one output on the host (firdecim.c:189-205: the dot
  * product right after the first of the M pushes) */
 static void lq_decim_exec1_host(lq_decim *q, const void *x, void *y)
 {
-    lq_mirror_need_host(&q->hm, q->d_hist[q->cur], q->ctx.stream);
-    lq_mirror_append(&q->hm, x, q->M);
-    lq_host_tdot(q->kind, q->hg, lq_mirror_ptr(&q->hm), q->hlen, y);   /* the hlen-sample window, oldest first */
-    lq_mirror_commit(&q->hm, q->M);
+    const unsigned char *w = lq_hist_append(&q->hist, x, q->M, q->ctx.stream);
+    lq_host_tdot(q->kind, q->hg, w, q->hlen, y);   /* the hlen-sample window, oldest first */
+    lq_hist_commit(&q->hist, q->M);
 }
 
 /* single: the call is firdecim_*_execute; execute_block always runs on the GPU */
@@ -177,31 +177,19 @@ static void lq_decim_block(lq_decim *q, const void *x, unsigned long long nout, 
     NAME NAME##_create_kaiser(unsigned int _M, unsigned int _m, float _As)                          \
     {                                                                                               \
         unsigned int n;                                                                             \
-        float *hf = lq_decim_kaiser(#NAME, _M, _m, _As, &n);                                        \
-        TC *hc = (TC *)lq_xmalloc(n * sizeof(TC));                                                  \
-        for (unsigned int i = 0; i < n; i++) hc[i] = (TC)hf[i];                                     \
-        NAME q = NAME##_create(_M, hc, n - 1);                                                      \
-        free(hf);                                                                                   \
-        free(hc);                                                                                   \
+        float *h = lq_mrate_kaiser(#NAME, "decim", _M, _m, _As, &n);                                \
+        h = lq_taps_from_real(KIND, h, n);                                                          \
+        NAME q = NAME##_create(_M, (TC *)h, n - 1);                                                 \
+        free(h);                                                                                    \
         return q;                                                                                   \
     }                                                                                               \
-    /* firdecim.c:126-160: 2Mm+1 taps from liquid_firdes_prototype */                               \
     NAME NAME##_create_prototype(int _type, unsigned int _M, unsigned int _m, float _beta, float _dt) \
     {                                                                                               \
-        if (_M < 2) LQ_FAIL("error: " #NAME "_create_prototype(), decimation factor must be greater than 1\n"); \
-        if (_m == 0) LQ_FAIL("error: " #NAME "_create_prototype(), filter delay must be greater than 0\n"); \
-        if (_beta < 0.0f || _beta > 1.0f)                                                           \
-            LQ_FAIL("error: " #NAME "_create_prototype(), filter excess bandwidth factor must be in [0,1]\n"); \
-        if (_dt < -1.0f || _dt > 1.0f)                                                              \
-            LQ_FAIL("error: " #NAME "_create_prototype(), filter fractional sample delay must be in [-1,1]\n"); \
-        const unsigned int n = 2 * _M * _m + 1;                                                     \
-        float *hf = (float *)lq_xmalloc(n * sizeof(float));                                         \
-        TC *hc = (TC *)lq_xmalloc(n * sizeof(TC));                                                  \
-        liquid_firdes_prototype((liquid_firfilt_type)_type, _M, _m, _beta, _dt, hf);                \
-        for (unsigned int i = 0; i < n; i++) hc[i] = (TC)hf[i];                                     \
-        NAME q = NAME##_create(_M, hc, n);                                                          \
-        free(hf);                                                                                   \
-        free(hc);                                                                                   \
+        unsigned int n;                                                                             \
+        float *h = lq_mrate_prototype(#NAME, "decimation", _type, _M, _m, _beta, _dt, &n);          \
+        h = lq_taps_from_real(KIND, h, n);                                                          \
+        NAME q = NAME##_create(_M, (TC *)h, n);                                                     \
+        free(h);                                                                                    \
         return q;                                                                                   \
     }                                                                                               \
     void NAME##_destroy(NAME _q)                                                                    \
@@ -234,26 +222,24 @@ typedef struct {
     unsigned int M, L, hlen;
     float *h;          /* padded prototype, M*L coefficients of csz bytes */
     void *d_hpoly;     /* M x L: hpoly[p*L + l] = h'[p + l*M] */
-    void *d_hist[2];   /* last L-1 inputs */
-    int cur;
+    lq_hist hist;      /* last L-1 inputs; mirrored for the small-call mode */
     float *hpoly;      /* host copy of the M x L phase taps */
     float *hgp;        /* the phases reversed and expanded for the host path, hgs floats apart */
     size_t hgs;
-    lq_mirror hm;      /* host copy of the history (small-call mode) */
     lq_ctx ctx;
     lq_devbuf xbuf, ybuf;
 } lq_interp;
 
 static lq_interp *lq_interp_create(int kind, unsigned int M, const float *h, unsigned int hlen)
 {
-    if (M < 2) LQ_FAIL("error: firinterp_%s_create(), interp factor must be greater than 1\n", lq_ext[kind]);
+    if (M < 2) LQ_FAIL("error: firinterp_%s_create(), interp factor must be greater than 1\n", lq_ext(kind));
     if (hlen < M)
-        LQ_FAIL("error: firinterp_%s_create(), filter length cannot be less than interp factor\n", lq_ext[kind]);
+        LQ_FAIL("error: firinterp_%s_create(), filter length cannot be less than interp factor\n", lq_ext(kind));
     lqrt_require_device("firinterp_create");
     lq_interp *q = (lq_interp *)lq_xmalloc(sizeof(*q));
     q->kind = kind;
-    q->esz = kind == LQ_RRRF ? 4 : 8;
-    q->csz = kind == LQ_CCCF ? 8 : 4;
+    q->esz = lq_esz(kind);
+    q->csz = lq_csz(kind);
     const size_t cf = q->csz / 4;       /* floats per coefficient */
     q->M = M;
     q->L = 0;
@@ -268,8 +254,7 @@ static lq_interp *lq_interp_create(int kind, unsigned int M, const float *h, uns
     lq_ctx_init(&q->ctx);
     q->d_hpoly = lqrt_malloc(q->hlen * q->csz);
     lqrt_h2d(q->d_hpoly, hp, q->hlen * q->csz, q->ctx.stream);
-    q->d_hist[0] = lqrt_malloc((size_t)q->L * q->esz);
-    q->d_hist[1] = lqrt_malloc((size_t)q->L * q->esz);
+    lq_hist_init(&q->hist, q->L - 1, q->esz, LQ_HIST_MIRROR);
     lqrt_sync(q->ctx.stream);
     q->hpoly = hp;
     q->hgs = (size_t)q->L * (kind == LQ_RRRF ? 1 : (kind == LQ_CRCF ? 2 : 4));
@@ -279,31 +264,17 @@ static lq_interp *lq_interp_create(int kind, unsigned int M, const float *h, uns
         memcpy(q->hgp + p * q->hgs, g, q->hgs * sizeof(float));
         free(g);
     }
-    lq_mirror_init(&q->hm, q->L - 1, q->esz);
     return q;
-}
-
-static float *lq_interp_kaiser(const char *who, unsigned int M, unsigned int m, float As, unsigned int *n)
-{
-    if (M < 2) LQ_FAIL("error: %s_create_kaiser(), interp factor must be greater than 1\n", who);
-    if (m == 0) LQ_FAIL("error: %s_create_kaiser(), filter delay must be greater than 0\n", who);
-    if (As < 0.0f) LQ_FAIL("error: %s_create_kaiser(), stop-band attenuation must be positive\n", who);
-    *n = 2 * M * m + 1;
-    float *hf = (float *)lq_xmalloc(*n * sizeof(float));
-    lq_firdes_kaiser(*n, 0.5f / (float)M, As, 0.0f, hf);
-    return hf;
 }
 
 static void lq_interp_destroy(lq_interp *q)
 {
     lqrt_sync(q->ctx.stream);
     lqrt_free(q->d_hpoly);
-    lqrt_free(q->d_hist[0]);
-    lqrt_free(q->d_hist[1]);
+    lq_hist_free(&q->hist);
     lq_devbuf_free(&q->xbuf);
     lq_devbuf_free(&q->ybuf);
     lq_ctx_free(&q->ctx);
-    lq_mirror_free(&q->hm);
     free(q->hpoly);
     free(q->hgp);
     free(q->h);
@@ -317,37 +288,25 @@ static void lq_interp_print(lq_interp *q)
     printf("    h_len   :   %u\n", q->hlen);
 }
 
-static void lq_interp_reset(lq_interp *q)
-{
-    lqrt_memset(q->d_hist[0], (size_t)q->L * q->esz, q->ctx.stream);
-    lqrt_memset(q->d_hist[1], (size_t)q->L * q->esz, q->ctx.stream);
-    lqrt_sync(q->ctx.stream);
-    lq_mirror_zero(&q->hm);
-}
+static void lq_interp_reset(lq_interp *q) { lq_hist_zero(&q->hist, q->ctx.stream); }
 
 static void lq_interp_block_dev(lq_interp *q, const void *dx, unsigned long long n, void *dy)
 {
     if (n == 0) return;
-    lq_mirror_need_dev(&q->hm, q->d_hist[q->cur], q->ctx.stream);
-    q->hm.host_valid = 0;
-    void *hold = q->d_hist[q->cur], *hnew = q->d_hist[q->cur ^ 1];
+    void *hold = lq_hist_dev(&q->hist, q->ctx.stream), *hnew = lq_hist_next(&q->hist);
     lqk_firinterp(q->kind, q->d_hpoly, q->M, q->L, 1.0f, 0.0f, hold, dx, n, dy, q->ctx.stream);
-    if (q->L > 1) {
-        lqk_window_append(q->kind != LQ_RRRF, hold, q->L - 1, dx, n, hnew, q->ctx.stream);
-        q->cur ^= 1;
-    }
+    if (q->L > 1) lqk_window_append(q->kind != LQ_RRRF, hold, q->L - 1, dx, n, hnew, q->ctx.stream);
+    lq_hist_flip(&q->hist);
 }
 
 /* small-call mode: the M outputs of one input on the host (firinterp.c:187-198:
  * bank p of the polyphase filter over the last L inputs) */
 static void lq_interp_exec1_host(lq_interp *q, const void *x, void *y)
 {
-    lq_mirror_need_host(&q->hm, q->d_hist[q->cur], q->ctx.stream);
-    lq_mirror_append(&q->hm, x, 1);
-    const unsigned char *w = lq_mirror_ptr(&q->hm);
+    const unsigned char *w = lq_hist_append(&q->hist, x, 1, q->ctx.stream);
     for (unsigned int p = 0; p < q->M; p++)   /* bank p over the L-sample window, oldest first */
         lq_host_tdot(q->kind, q->hgp + p * q->hgs, w, q->L, (unsigned char *)y + p * q->esz);
-    lq_mirror_commit(&q->hm, 1);
+    lq_hist_commit(&q->hist, 1);
 }
 
 /* single: the call is firinterp_*_execute; execute_block always runs on the GPU */
@@ -378,31 +337,19 @@ static void lq_interp_block(lq_interp *q, const void *x, unsigned long long n, v
     NAME NAME##_create_kaiser(unsigned int _M, unsigned int _m, float _As)                          \
     {                                                                                               \
         unsigned int n;                                                                             \
-        float *hf = lq_interp_kaiser(#NAME, _M, _m, _As, &n);                                       \
-        TC *hc = (TC *)lq_xmalloc(n * sizeof(TC));                                                  \
-        for (unsigned int i = 0; i < n; i++) hc[i] = (TC)hf[i];                                     \
-        NAME q = NAME##_create(_M, hc, n - 1);                                                      \
-        free(hf);                                                                                   \
-        free(hc);                                                                                   \
+        float *h = lq_mrate_kaiser(#NAME, "interp", _M, _m, _As, &n);                               \
+        h = lq_taps_from_real(KIND, h, n);                                                          \
+        NAME q = NAME##_create(_M, (TC *)h, n - 1);                                                 \
+        free(h);                                                                                    \
         return q;                                                                                   \
     }                                                                                               \
-    /* firinterp.c:124-158: 2Mm+1 taps from liquid_firdes_prototype */                              \
     NAME NAME##_create_prototype(int _type, unsigned int _M, unsigned int _m, float _beta, float _dt) \
     {                                                                                               \
-        if (_M < 2) LQ_FAIL("error: " #NAME "_create_prototype(), interp factor must be greater than 1\n"); \
-        if (_m == 0) LQ_FAIL("error: " #NAME "_create_prototype(), filter delay must be greater than 0\n"); \
-        if (_beta < 0.0f || _beta > 1.0f)                                                           \
-            LQ_FAIL("error: " #NAME "_create_prototype(), filter excess bandwidth factor must be in [0,1]\n"); \
-        if (_dt < -1.0f || _dt > 1.0f)                                                              \
-            LQ_FAIL("error: " #NAME "_create_prototype(), filter fractional sample delay must be in [-1,1]\n"); \
-        const unsigned int n = 2 * _M * _m + 1;                                                     \
-        float *hf = (float *)lq_xmalloc(n * sizeof(float));                                         \
-        TC *hc = (TC *)lq_xmalloc(n * sizeof(TC));                                                  \
-        liquid_firdes_prototype((liquid_firfilt_type)_type, _M, _m, _beta, _dt, hf);                \
-        for (unsigned int i = 0; i < n; i++) hc[i] = (TC)hf[i];                                     \
-        NAME q = NAME##_create(_M, hc, n);                                                          \
-        free(hf);                                                                                   \
-        free(hc);                                                                                   \
+        unsigned int n;                                                                             \
+        float *h = lq_mrate_prototype(#NAME, "interp", _type, _M, _m, _beta, _dt, &n);              \
+        h = lq_taps_from_real(KIND, h, n);                                                          \
+        NAME q = NAME##_create(_M, (TC *)h, n);                                                     \
+        free(h);                                                                                    \
         return q;                                                                                   \
     }                                                                                               \
     void NAME##_destroy(NAME _q)                                                                    \

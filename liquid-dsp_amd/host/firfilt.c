@@ -8,10 +8,10 @@
  *
  * State model.  The filter state is the window of the last HP samples
  * (HP = length padded to the kernel's chunk class), oldest first, kept on
- * the device (two ping-pong buffers) with a host mirror for the per-sample
- * push() path.  Exactly one copy is authoritative at a time; the other is
- * refreshed lazily.  Every output sample, including the per-sample
- * execute(), is computed by a HIP kernel.
+ * the device with a pinned host mirror for the per-sample push() path
+ * (lq_hist, PINNED).  Exactly one copy is authoritative at a time; the other
+ * is refreshed lazily.  Outside the small-call mode every output sample,
+ * including the per-sample execute(), is computed by a HIP kernel.
  */
 #include <complex.h>
 #include <math.h>
@@ -27,17 +27,11 @@ struct lq_firfilt_s {
     float *hg;         /* reversed, expanded for the host path (lq_host_taps) */
     void *d_hpad;      /* device, zero padded to HP */
     lqk_fir_desc d;
-    void *d_win[2];    /* device windows, HP samples each */
-    int cur;
-    unsigned char *h_win; /* host mirror: the window is HP samples at h_win + hoff * esz, */
-    size_t hoff;          /* pushes append after it (capacity LQ_FIR_HCAP windows) */
-    int host_valid, dev_valid;
+    lq_hist win;       /* the window, HP samples; pinned: the per-sample execute() reads it in place */
     lq_ctx ctx;
     lq_devbuf xbuf, ybuf, scratch, one;
     const char *who;   /* the public object name, for error messages */
 };
-
-#define LQ_FIR_HCAP 8   /* host window buffer, in windows: a memmove every 7 HP pushes */
 
 static void lq_firfilt_layout(lq_firfilt *q, unsigned int n)
 {
@@ -65,22 +59,13 @@ static void lq_firfilt_layout(lq_firfilt *q, unsigned int n)
 static void lq_firfilt_alloc_state(lq_firfilt *q)
 {
     q->d_hpad = lqrt_malloc((size_t)q->HP * q->csz);
-    q->d_win[0] = lqrt_malloc((size_t)q->HP * q->esz);
-    q->d_win[1] = lqrt_malloc((size_t)q->HP * q->esz);
-    /* pinned: the per-sample execute() reads it in place (zero copy) */
-    q->h_win = (unsigned char *)lqrt_host_alloc((size_t)LQ_FIR_HCAP * q->HP * q->esz);
-    memset(q->h_win, 0, (size_t)q->HP * q->esz);
-    q->hoff = 0;
-    q->cur = 0;
-    q->host_valid = q->dev_valid = 1;
+    lq_hist_init(&q->win, q->HP, q->esz, LQ_HIST_PINNED);
 }
 
 static void lq_firfilt_free_state(lq_firfilt *q)
 {
     lqrt_free(q->d_hpad);
-    lqrt_free(q->d_win[0]);
-    lqrt_free(q->d_win[1]);
-    lqrt_host_free(q->h_win);
+    lq_hist_free(&q->win);
 }
 
 static void lq_firfilt_upload_coefs(lq_firfilt *q)
@@ -110,8 +95,8 @@ lq_firfilt *lq_firfilt_create(int kind, const float *h, unsigned int n, const ch
     lqrt_require_device(who);
     lq_firfilt *q = (lq_firfilt *)lq_xmalloc(sizeof(*q));
     q->kind = kind;
-    q->esz = kind == LQ_RRRF ? sizeof(float) : 2 * sizeof(float);
-    q->csz = kind == LQ_CCCF ? 2 * sizeof(float) : sizeof(float);
+    q->esz = lq_esz(kind);
+    q->csz = lq_csz(kind);
     q->d.kind = kind;
     q->d.scale_re = 1.0f;
     q->d.scale_im = 0.0f;
@@ -160,20 +145,11 @@ void lq_firfilt_destroy(lq_firfilt *q)
     free(q);
 }
 
-void lq_firfilt_reset(lq_firfilt *q)
-{
-    lqrt_memset(q->d_win[0], (size_t)q->HP * q->esz, q->ctx.stream);
-    lqrt_memset(q->d_win[1], (size_t)q->HP * q->esz, q->ctx.stream);
-    lqrt_sync(q->ctx.stream);
-    q->hoff = 0;
-    memset(q->h_win, 0, (size_t)q->HP * q->esz);
-    q->host_valid = q->dev_valid = 1;
-}
+void lq_firfilt_reset(lq_firfilt *q) { lq_hist_zero(&q->win, q->ctx.stream); }
 
 void lq_firfilt_print(lq_firfilt *q)
 {
-    static const char *ext[] = {"rrrf", "crcf", "cccf"};
-    printf("firfilt_%s:\n", ext[q->kind]);
+    printf("firfilt_%s:\n", lq_ext(q->kind));
     for (unsigned int i = 0; i < q->hlen; i++) {
         if (q->kind == LQ_CCCF)
             printf("  h(%3u) = %12.8f + j*%12.8f\n", i + 1, q->h[2 * i], q->h[2 * i + 1]);
@@ -192,36 +168,12 @@ void lq_firfilt_set_scale(lq_firfilt *q, float re, float im)
     q->d.scale_im = im;
 }
 
-static void lq_firfilt_need_host(lq_firfilt *q)
-{
-    if (q->host_valid) return;
-    q->hoff = 0;
-    lqrt_d2h(q->h_win, q->d_win[q->cur], (size_t)q->HP * q->esz, q->ctx.stream);
-    lqrt_sync(q->ctx.stream);
-    q->host_valid = 1;
-}
-
-static void lq_firfilt_need_dev(lq_firfilt *q)
-{
-    if (q->dev_valid) return;
-    lqrt_h2d(q->d_win[q->cur], q->h_win + q->hoff * q->esz, (size_t)q->HP * q->esz, q->ctx.stream);
-    q->dev_valid = 1;
-}
-
+/* the window moves up one sample in the host mirror (the reference's window.c
+ * likewise appends and only moves the window back when its buffer is full) */
 void lq_firfilt_push(lq_firfilt *q, const void *x)
 {
-    lq_firfilt_need_host(q);
-    /* append after the window; the window moves up one sample, and only
-     * when the buffer is full do its last HP-1 samples move back to the
-     * start (the reference's window.c does the same with its 2^k + len - 1
-     * buffer) */
-    if (q->hoff + q->HP == (size_t)LQ_FIR_HCAP * q->HP) {
-        memmove(q->h_win, q->h_win + (q->hoff + 1) * q->esz, (size_t)(q->HP - 1) * q->esz);
-        q->hoff = (size_t)-1;
-    }
-    memcpy(q->h_win + (q->hoff + q->HP) * q->esz, x, q->esz);
-    q->hoff++;
-    q->dev_valid = 0;
+    lq_hist_append(&q->win, x, 1, q->ctx.stream);
+    lq_hist_commit(&q->win, 1);
 }
 
 /* one output from the current window: the kernel reads the window where it
@@ -231,26 +183,16 @@ void lq_firfilt_push(lq_firfilt *q, const void *x)
  * stream sync) */
 void lq_firfilt_execute(lq_firfilt *q, void *y)
 {
-    if (lq_small_host()) {   /* opt-in host path (lq_small.c): the window's newest sample is h_win[HP-1] */
-        lq_firfilt_need_host(q);
-        float v[2];
+    if (lq_small_host()) {   /* the host path (lq_small.c) */
         /* the last hlen window samples, oldest first, against the reversed taps */
-        lq_host_tdot(q->kind, q->hg, q->h_win + (q->hoff + q->HP - q->hlen) * q->esz, q->hlen, v);
-        if (q->kind == LQ_RRRF) {
-            *(float *)y = v[0] * q->d.scale_re;
-        } else if (q->kind == LQ_CRCF) {   /* firfilt.c:337: real scale per component */
-            ((float *)y)[0] = v[0] * q->d.scale_re;
-            ((float *)y)[1] = v[1] * q->d.scale_re;
-        } else {
-            ((float *)y)[0] = v[0] * q->d.scale_re - v[1] * q->d.scale_im;
-            ((float *)y)[1] = v[0] * q->d.scale_im + v[1] * q->d.scale_re;
-        }
+        const unsigned char *w = lq_hist_host(&q->win, q->ctx.stream) + (size_t)(q->HP - q->hlen) * q->esz;
+        lq_host_tdot(q->kind, q->hg, w, q->hlen, y);
+        lq_host_scale(q->kind, q->d.scale_re, q->d.scale_im, (float *)y);
         return;
     }
-    const void *win = q->dev_valid ? q->d_win[q->cur] : (const void *)(q->h_win + q->hoff * q->esz);
     unsigned *flag, seq;
     void *py = lq_sig_out(&q->ctx, q->esz, &flag, &seq);
-    lqk_fir_single(&q->d, win, py, flag, seq, q->ctx.stream);
+    lqk_fir_single(&q->d, lq_hist_read(&q->win), py, flag, seq, q->ctx.stream);
     lq_sig_wait(&q->ctx, y, q->esz, seq);
 }
 
@@ -267,16 +209,13 @@ void lq_firfilt_execute(lq_firfilt *q, void *y)
 void lq_firfilt_execute_block_dev(lq_firfilt *q, const void *dx, unsigned long long n, void *dy)
 {
     if (n == 0) return;
-    lq_firfilt_need_dev(q);
-    void *wold = q->d_win[q->cur];
-    void *wnew = q->d_win[q->cur ^ 1];
+    void *wold = lq_hist_dev(&q->win, q->ctx.stream), *wnew = lq_hist_next(&q->win);
     void *scr = NULL;
     if (dx == dy) scr = lq_devbuf_get(&q->scratch, lqk_firfilt_scratch_bytes(&q->d, n));
     /* the window update: inside the matrix-core kernel, else launched first */
     const lqk_hist_job job = {wold, dx, n, wnew, q->HP};
     lqk_firfilt(&q->d, wold, dx, n, dy, scr, &job, q->ctx.stream);
-    q->cur ^= 1;
-    q->host_valid = 0;
+    lq_hist_flip(&q->win);
 }
 
 void lq_firfilt_execute_block(lq_firfilt *q, const void *x, unsigned long long n, void *y)
@@ -323,36 +262,42 @@ lq_ctx *lq_firfilt_ctx(lq_firfilt *q) { return &q->ctx; }
 
 /* ----------------------------------------------------------------- typed front ends */
 
+/* from real design taps hf (taken over) */
+static lq_firfilt *lq_firfilt_create_real(int kind, float *hf, unsigned int n, const char *who)
+{
+    float *h = lq_taps_from_real(kind, hf, n);
+    lq_firfilt *f = lq_firfilt_create(kind, h, n, who);
+    free(h);
+    return f;
+}
+
 #define LQ_FIRFILT_FRONT(NAME, KIND, TO, TC, TI, SCALE_RE, SCALE_IM)                                \
     struct NAME##_s {                                                                               \
         lq_firfilt *f;                                                                              \
     };                                                                                              \
-    NAME NAME##_create(TC *_h, unsigned int _n)                                                     \
+    static NAME NAME##_wrap(lq_firfilt *f)                                                          \
     {                                                                                               \
         NAME q = (NAME)lq_xmalloc(sizeof(*q));                                                      \
-        q->f = lq_firfilt_create(KIND, (const float *)_h, _n, #NAME);                               \
+        q->f = f;                                                                                   \
         return q;                                                                                   \
+    }                                                                                               \
+    NAME NAME##_create(TC *_h, unsigned int _n)                                                     \
+    {                                                                                               \
+        return NAME##_wrap(lq_firfilt_create(KIND, (const float *)_h, _n, #NAME));                  \
     }                                                                                               \
     NAME NAME##_create_kaiser(unsigned int _n, float _fc, float _As, float _mu)                     \
     {                                                                                               \
         if (_n == 0) LQ_FAIL("error: " #NAME "_create_kaiser(), filter length must be greater than zero\n"); \
         float *hf = (float *)lq_xmalloc(_n * sizeof(float));                                        \
-        TC *hc = (TC *)lq_xmalloc(_n * sizeof(TC));                                                 \
         lq_firdes_kaiser(_n, _fc, _As, _mu, hf);                                                    \
-        for (unsigned int i = 0; i < _n; i++) hc[i] = (TC)hf[i];                                    \
-        NAME q = NAME##_create(hc, _n);                                                             \
-        free(hf);                                                                                   \
-        free(hc);                                                                                   \
-        return q;                                                                                   \
+        return NAME##_wrap(lq_firfilt_create_real(KIND, hf, _n, #NAME));                            \
     }                                                                                               \
     NAME NAME##_create_rect(unsigned int _n)                                                        \
     {                                                                                               \
         if (_n == 0 || _n > 1024) LQ_FAIL("error: " #NAME "_create_rect(), filter length must be in [1,1024]\n"); \
-        TC *hc = (TC *)lq_xmalloc(_n * sizeof(TC));                                                 \
-        for (unsigned int i = 0; i < _n; i++) hc[i] = (TC)1.0f;                                     \
-        NAME q = NAME##_create(hc, _n);                                                             \
-        free(hc);                                                                                   \
-        return q;                                                                                   \
+        float *hf = (float *)lq_xmalloc(_n * sizeof(float));                                        \
+        for (unsigned int i = 0; i < _n; i++) hf[i] = 1.0f;                                         \
+        return NAME##_wrap(lq_firfilt_create_real(KIND, hf, _n, #NAME));                            \
     }                                                                                               \
     /* firfilt.c:140-171: 2km+1 taps from liquid_firdes_prototype */                                \
     NAME NAME##_create_rnyquist(int _type, unsigned int _k, unsigned int _m, float _beta, float _mu)\
@@ -363,13 +308,8 @@ lq_ctx *lq_firfilt_ctx(lq_firfilt *q) { return &q->ctx; }
             LQ_FAIL("error: " #NAME "_create_rnyquist(), filter excess bandwidth factor must be in [0,1]\n");\
         const unsigned int n = 2 * _k * _m + 1;                                                     \
         float *hf = (float *)lq_xmalloc(n * sizeof(float));                                         \
-        TC *hc = (TC *)lq_xmalloc(n * sizeof(TC));                                                  \
         liquid_firdes_prototype((liquid_firfilt_type)_type, _k, _m, _beta, _mu, hf);                \
-        for (unsigned int i = 0; i < n; i++) hc[i] = (TC)hf[i];                                     \
-        NAME q = NAME##_create(hc, n);                                                              \
-        free(hf);                                                                                   \
-        free(hc);                                                                                   \
-        return q;                                                                                   \
+        return NAME##_wrap(lq_firfilt_create_real(KIND, hf, n, #NAME));                             \
     }                                                                                               \
     NAME NAME##_recreate(NAME _q, TC *_h, unsigned int _n)                                          \
     {                                                                                               \

@@ -66,7 +66,7 @@ firhilbf firhilbf_create(unsigned int _m, float _As)
         for (int w = 0; w < 2; w++) q->d_w[b][w] = lqrt_malloc(2 * _m * sizeof(float));   /* zeroed */
     lqrt_h2d(q->d_taps, q->hq, 2 * _m * sizeof(float), q->ctx.stream);
     lqrt_sync(q->ctx.stream);
-    for (int w = 0; w < 2; w++) lq_mirror_init(&q->wm[w], 2 * _m, sizeof(float));
+    for (int w = 0; w < 2; w++) lq_mirror_init(&q->wm[w], 2 * _m, sizeof(float), 0);
     return o;
 }
 

@@ -15,8 +15,6 @@
 
 #include "lq_host.h"
 
-static const char *lq_ext[] = {"rrrf", "crcf", "cccf"};
-
 typedef struct {
     int kind;
     size_t esz, csz;
@@ -24,10 +22,7 @@ typedef struct {
     float sre, sim;
     float *hpoly;                 /* M x L coefficients, hpoly[i*L + n] = h[i + n*M] */
     void *d_hpoly;
-    void *d_win[2];               /* last L inputs, oldest first */
-    int cur;
-    unsigned char *h_win;         /* host mirror for push() */
-    int host_valid, dev_valid;
+    lq_hist win;                  /* last L inputs, oldest first; pinned: execute() reads it in place */
     lq_ctx ctx;
     lq_devbuf xbuf, ybuf, one;
 } lq_pfb;
@@ -41,15 +36,15 @@ static void lq_pfb_load(lq_pfb *q, const float *h)
 
 static lq_pfb *lq_pfb_create(int kind, unsigned int M, const float *h, unsigned int hlen)
 {
-    if (M == 0) LQ_FAIL("error: firpfb_%s_create(), number of filters must be greater than zero\n", lq_ext[kind]);
-    if (hlen == 0) LQ_FAIL("error: firpfb_%s_create(), filter length must be greater than zero\n", lq_ext[kind]);
+    if (M == 0) LQ_FAIL("error: firpfb_%s_create(), number of filters must be greater than zero\n", lq_ext(kind));
+    if (hlen == 0) LQ_FAIL("error: firpfb_%s_create(), filter length must be greater than zero\n", lq_ext(kind));
     if (hlen < M)
-        LQ_FAIL("error: firpfb_%s_create(), filter length must be at least the number of filters\n", lq_ext[kind]);
+        LQ_FAIL("error: firpfb_%s_create(), filter length must be at least the number of filters\n", lq_ext(kind));
     lqrt_require_device("firpfb_create");
     lq_pfb *q = (lq_pfb *)lq_xmalloc(sizeof(*q));
     q->kind = kind;
-    q->esz = kind == LQ_RRRF ? 4 : 8;
-    q->csz = kind == LQ_CCCF ? 8 : 4;
+    q->esz = lq_esz(kind);
+    q->csz = lq_csz(kind);
     q->M = M;
     q->hlen = hlen;
     q->L = hlen / M;
@@ -60,13 +55,17 @@ static lq_pfb *lq_pfb_create(int kind, unsigned int M, const float *h, unsigned 
     lq_ctx_init(&q->ctx);
     q->d_hpoly = lqrt_malloc((size_t)M * q->L * q->csz);
     lqrt_h2d(q->d_hpoly, q->hpoly, (size_t)M * q->L * q->csz, q->ctx.stream);
-    q->d_win[0] = lqrt_malloc((size_t)q->L * q->esz);
-    q->d_win[1] = lqrt_malloc((size_t)q->L * q->esz);
-    /* pinned: execute() reads it in place (zero copy) */
-    q->h_win = (unsigned char *)lqrt_host_alloc((size_t)q->L * q->esz);
-    memset(q->h_win, 0, (size_t)q->L * q->esz);
-    q->host_valid = q->dev_valid = 1;
+    lq_hist_init(&q->win, q->L, q->esz, LQ_HIST_PINNED);
     lqrt_sync(q->ctx.stream);
+    return q;
+}
+
+/* from real design taps hf (taken over) */
+static lq_pfb *lq_pfb_create_real(int kind, unsigned int M, float *hf, unsigned int n)
+{
+    float *h = lq_taps_from_real(kind, hf, n);
+    lq_pfb *q = lq_pfb_create(kind, M, h, n);
+    free(h);
     return q;
 }
 
@@ -112,14 +111,12 @@ static void lq_pfb_destroy(lq_pfb *q)
 {
     lqrt_sync(q->ctx.stream);
     lqrt_free(q->d_hpoly);
-    lqrt_free(q->d_win[0]);
-    lqrt_free(q->d_win[1]);
+    lq_hist_free(&q->win);
     lq_devbuf_free(&q->xbuf);
     lq_devbuf_free(&q->ybuf);
     lq_devbuf_free(&q->one);
     lq_ctx_free(&q->ctx);
     free(q->hpoly);
-    lqrt_host_free(q->h_win);
     free(q);
 }
 
@@ -137,60 +134,36 @@ static void lq_pfb_print(lq_pfb *q)
     for (unsigned int i = 0; i < q->M; i++) printf("  bank %3u: \n", i);
 }
 
-static void lq_pfb_reset(lq_pfb *q)
-{
-    lqrt_memset(q->d_win[0], (size_t)q->L * q->esz, q->ctx.stream);
-    lqrt_memset(q->d_win[1], (size_t)q->L * q->esz, q->ctx.stream);
-    lqrt_sync(q->ctx.stream);
-    memset(q->h_win, 0, (size_t)q->L * q->esz);
-    q->host_valid = q->dev_valid = 1;
-}
-
-static void lq_pfb_need_host(lq_pfb *q)
-{
-    if (q->host_valid) return;
-    lqrt_d2h(q->h_win, q->d_win[q->cur], (size_t)q->L * q->esz, q->ctx.stream);
-    lqrt_sync(q->ctx.stream);
-    q->host_valid = 1;
-}
-
-static void lq_pfb_need_dev(lq_pfb *q)
-{
-    if (q->dev_valid) return;
-    lqrt_h2d(q->d_win[q->cur], q->h_win, (size_t)q->L * q->esz, q->ctx.stream);
-    q->dev_valid = 1;
-}
+static void lq_pfb_reset(lq_pfb *q) { lq_hist_zero(&q->win, q->ctx.stream); }
 
 static void lq_pfb_push(lq_pfb *q, const void *x)
 {
-    lq_pfb_need_host(q);
-    memmove(q->h_win, q->h_win + q->esz, (size_t)(q->L - 1) * q->esz);
-    memcpy(q->h_win + (size_t)(q->L - 1) * q->esz, x, q->esz);
-    q->dev_valid = 0;
+    lq_hist_append(&q->win, x, 1, q->ctx.stream);
+    lq_hist_commit(&q->win, 1);
 }
 
+/* the kernel reads the window where it is authoritative: in place from the
+ * pinned host mirror after push()es, or the device copy after a block */
 static void lq_pfb_execute(lq_pfb *q, unsigned int i, void *y)
 {
     if (i >= q->M) LQ_FAIL("error: firpfb_execute(), filterbank index (%u) exceeds maximum (%u)\n", i, q->M);
-    const void *win = q->dev_valid ? q->d_win[q->cur] : (const void *)q->h_win;
     unsigned *flag, seq;
     void *py = lq_sig_out(&q->ctx, q->esz, &flag, &seq);
-    lqk_firpfb_single(q->kind, q->d_hpoly, q->L, i, win, q->sre, q->sim, py, flag, seq, q->ctx.stream);
+    lqk_firpfb_single(q->kind, q->d_hpoly, q->L, i, lq_hist_read(&q->win), q->sre, q->sim, py, flag, seq,
+                      q->ctx.stream);
     lq_sig_wait(&q->ctx, y, q->esz, seq);
 }
 
 static void lq_pfb_block_dev(lq_pfb *q, const void *dx, unsigned long long n, void *dy)
 {
     if (n == 0) return;
-    lq_pfb_need_dev(q);
-    void *wold = q->d_win[q->cur], *wnew = q->d_win[q->cur ^ 1];
+    void *wold = lq_hist_dev(&q->win, q->ctx.stream), *wnew = lq_hist_next(&q->win);
     /* bank outputs after each push: the interpolator kernel (y[t*M+i]) with
      * the window's last L-1 samples as history */
     lqk_firinterp(q->kind, q->d_hpoly, q->M, q->L, q->sre, q->sim, (const char *)wold + q->esz, dx, n, dy,
                   q->ctx.stream);
     lqk_window_append(q->kind != LQ_RRRF, wold, q->L, dx, n, wnew, q->ctx.stream);
-    q->cur ^= 1;
-    q->host_valid = 0;
+    lq_hist_flip(&q->win);
 }
 
 static void lq_pfb_block(lq_pfb *q, const void *x, unsigned long long n, void *y)
@@ -207,45 +180,34 @@ static void lq_pfb_block(lq_pfb *q, const void *x, unsigned long long n, void *y
     struct NAME##_s {                                                                               \
         lq_pfb *e;                                                                                  \
     };                                                                                              \
-    NAME NAME##_create(unsigned int _M, TC *_h, unsigned int _h_len)                                \
+    static NAME NAME##_wrap(lq_pfb *e)                                                              \
     {                                                                                               \
         NAME q = (NAME)lq_xmalloc(sizeof(*q));                                                      \
-        q->e = lq_pfb_create(KIND, _M, (const float *)_h, _h_len);                                  \
+        q->e = e;                                                                                   \
         return q;                                                                                   \
+    }                                                                                               \
+    NAME NAME##_create(unsigned int _M, TC *_h, unsigned int _h_len)                                \
+    {                                                                                               \
+        return NAME##_wrap(lq_pfb_create(KIND, _M, (const float *)_h, _h_len));                     \
     }                                                                                               \
     NAME NAME##_create_kaiser(unsigned int _M, unsigned int _m, float _fc, float _As)               \
     {                                                                                               \
         unsigned int n;                                                                             \
         float *hf = lq_pfb_kaiser(#NAME, _M, _m, _fc, _As, &n);                                     \
-        TC *hc = (TC *)lq_xmalloc(n * sizeof(TC));                                                  \
-        for (unsigned int i = 0; i < n; i++) hc[i] = (TC)hf[i];                                     \
-        NAME q = NAME##_create(_M, hc, n);                                                          \
-        free(hf);                                                                                   \
-        free(hc);                                                                                   \
-        return q;                                                                                   \
+        return NAME##_wrap(lq_pfb_create_real(KIND, _M, hf, n));                                    \
     }                                                                                               \
     /* firpfb.c:146-180 (d = 0) and :188-240 (d = 1: derivative bank) */                            \
     NAME NAME##_create_rnyquist(int _type, unsigned int _M, unsigned int _k, unsigned int _m, float _beta)\
     {                                                                                               \
         unsigned int n;                                                                             \
         float *hf = lq_pfb_rnyquist(#NAME, "_create_rnyquist", 0, _type, _M, _k, _m, _beta, &n);    \
-        TC *hc = (TC *)lq_xmalloc(n * sizeof(TC));                                                  \
-        for (unsigned int i = 0; i < n; i++) hc[i] = (TC)hf[i];                                     \
-        NAME q = NAME##_create(_M, hc, n);                                                          \
-        free(hf);                                                                                   \
-        free(hc);                                                                                   \
-        return q;                                                                                   \
+        return NAME##_wrap(lq_pfb_create_real(KIND, _M, hf, n));                                    \
     }                                                                                               \
     NAME NAME##_create_drnyquist(int _type, unsigned int _M, unsigned int _k, unsigned int _m, float _beta)\
     {                                                                                               \
         unsigned int n;                                                                             \
         float *hf = lq_pfb_rnyquist(#NAME, "_create_drnyquist", 1, _type, _M, _k, _m, _beta, &n);   \
-        TC *hc = (TC *)lq_xmalloc(n * sizeof(TC));                                                  \
-        for (unsigned int i = 0; i < n; i++) hc[i] = (TC)hf[i];                                     \
-        NAME q = NAME##_create(_M, hc, n);                                                          \
-        free(hf);                                                                                   \
-        free(hc);                                                                                   \
-        return q;                                                                                   \
+        return NAME##_wrap(lq_pfb_create_real(KIND, _M, hf, n));                                    \
     }                                                                                               \
     void NAME##_destroy(NAME _q)                                                                    \
     {                                                                                               \

@@ -18,7 +18,6 @@
 
 #include "lq_host.h"
 
-static const char *lq_ext[] = {"rrrf", "crcf", "cccf"};
 
 typedef struct {
     int kind, type;
@@ -26,8 +25,7 @@ typedef struct {
     size_t csz;        /* bytes per coefficient */
     float *h;
     void *d_hsub;      /* M x p: hsub[i*p + n] = h[i + n*M] */
-    void *d_hist[2];   /* analyzer: last (p-1)*M inputs */
-    int cur;
+    lq_hist hist;      /* analyzer: last (p-1)*M inputs */
     void *d_zstate;    /* synthesizer: last p-1 IFFT vectors */
     lq_ctx ctx;
     lq_devbuf xbuf, ybuf, zbuf;
@@ -35,7 +33,7 @@ typedef struct {
 
 static lq_pfbch *lq_pfbch_create(int kind, int type, unsigned int M, unsigned int p, const float *h)
 {
-    const char *e = lq_ext[kind];
+    const char *e = lq_ext(kind);
     if (type != LIQUID_ANALYZER && type != LIQUID_SYNTHESIZER)
         LQ_FAIL("error: firpfbch_%s_create(), invalid type %d\n", e, type);
     if (M == 0) LQ_FAIL("error: firpfbch_%s_create(), number of channels must be greater than 0\n", e);
@@ -46,7 +44,7 @@ static lq_pfbch *lq_pfbch_create(int kind, int type, unsigned int M, unsigned in
     q->type = type;
     q->M = M;
     q->p = p;
-    q->csz = kind == LQ_CCCF ? 8 : 4;
+    q->csz = lq_csz(kind);
     const size_t nh = (size_t)M * p, cw = q->csz / 4;
     q->h = (float *)lq_xmalloc(nh * q->csz);
     memcpy(q->h, h, nh * q->csz);
@@ -57,10 +55,8 @@ static lq_pfbch *lq_pfbch_create(int kind, int type, unsigned int M, unsigned in
     lq_ctx_init(&q->ctx);
     q->d_hsub = lqrt_malloc(nh * q->csz);
     lqrt_h2d(q->d_hsub, hsub, nh * q->csz, q->ctx.stream);
-    size_t hb = (size_t)(p - 1) * M * 8;
-    q->d_hist[0] = lqrt_malloc(hb);
-    q->d_hist[1] = lqrt_malloc(hb);
-    q->d_zstate = lqrt_malloc(hb);
+    lq_hist_init(&q->hist, (size_t)(p - 1) * M, 8, LQ_HIST_DEV);
+    q->d_zstate = lqrt_malloc((size_t)(p - 1) * M * 8);
     lqrt_sync(q->ctx.stream);
     free(hsub);
     return q;
@@ -83,8 +79,8 @@ static lq_pfbch *lq_pfbch_create_real(int kind, int type, unsigned int M, unsign
 
 static lq_pfbch *lq_pfbch_create_kaiser(int kind, int type, unsigned int M, unsigned int m, float As)
 {
-    if (M == 0) LQ_FAIL("error: firpfbch_%s_create_kaiser(), number of channels must be greater than 0\n", lq_ext[kind]);
-    if (m == 0) LQ_FAIL("error: firpfbch_%s_create_kaiser(), invalid filter size (must be greater than 0)\n", lq_ext[kind]);
+    if (M == 0) LQ_FAIL("error: firpfbch_%s_create_kaiser(), number of channels must be greater than 0\n", lq_ext(kind));
+    if (m == 0) LQ_FAIL("error: firpfbch_%s_create_kaiser(), invalid filter size (must be greater than 0)\n", lq_ext(kind));
     As = As < 0 ? -As : As;
     unsigned int n = 2 * M * m + 1;
     float *h = (float *)lq_xmalloc(n * sizeof(float));
@@ -96,7 +92,7 @@ static lq_pfbch *lq_pfbch_create_kaiser(int kind, int type, unsigned int M, unsi
 
 static lq_pfbch *lq_pfbch_create_rnyquist(int kind, int type, unsigned int M, unsigned int m, float beta, int ftype)
 {
-    const char *e = lq_ext[kind];
+    const char *e = lq_ext(kind);
     if (type != LIQUID_ANALYZER && type != LIQUID_SYNTHESIZER)
         LQ_FAIL("error: firpfbch_%s_create_rnyquist(), invalid type %d\n", e, type);
     if (M == 0) LQ_FAIL("error: firpfbch_%s_create_rnyquist(), number of channels must be greater than 0\n", e);
@@ -122,8 +118,7 @@ static void lq_pfbch_destroy(lq_pfbch *q)
 {
     lqrt_sync(q->ctx.stream);
     lqrt_free(q->d_hsub);
-    lqrt_free(q->d_hist[0]);
-    lqrt_free(q->d_hist[1]);
+    lq_hist_free(&q->hist);
     lqrt_free(q->d_zstate);
     lq_devbuf_free(&q->xbuf);
     lq_devbuf_free(&q->ybuf);
@@ -135,11 +130,8 @@ static void lq_pfbch_destroy(lq_pfbch *q)
 
 static void lq_pfbch_reset(lq_pfbch *q)
 {
-    size_t hb = (size_t)(q->p - 1) * q->M * 8;
-    lqrt_memset(q->d_hist[0], hb, q->ctx.stream);
-    lqrt_memset(q->d_hist[1], hb, q->ctx.stream);
-    lqrt_memset(q->d_zstate, hb, q->ctx.stream);
-    lqrt_sync(q->ctx.stream);
+    lqrt_memset(q->d_zstate, (size_t)(q->p - 1) * q->M * 8, q->ctx.stream);
+    lq_hist_zero(&q->hist, q->ctx.stream);
 }
 
 static void lq_pfbch_print(lq_pfbch *q)
@@ -159,12 +151,12 @@ static int lq_pfbch_an_few(lq_pfbch *q, const void *dx, unsigned long long nbloc
                            unsigned seq)
 {
     const unsigned int HL = (q->p - 1) * q->M;
-    void *hold = q->d_hist[q->cur], *hnew = q->d_hist[q->cur ^ 1];
+    void *hold = lq_hist_dev(&q->hist, q->ctx.stream), *hnew = lq_hist_next(&q->hist);
     const lqk_hist_job job = {hold, dx, nblocks * q->M, hnew, HL};
     if (!lqk_firpfbch_analyzer_few(q->kind == LQ_CCCF, q->M, q->p, q->d_hsub, hold, dx, nblocks, dy, HL ? &job : NULL,
                                    flag, seq, q->ctx.stream))
         return 0;
-    if (HL) q->cur ^= 1;
+    lq_hist_flip(&q->hist);
     return 1;
 }
 
@@ -174,11 +166,11 @@ static void lq_pfbch_block_dev(lq_pfbch *q, const void *dx, unsigned long long n
     const int ctaps = q->kind == LQ_CCCF;
     if (q->type == LIQUID_ANALYZER) {
         if (lq_pfbch_an_few(q, dx, nblocks, dy, NULL, 0)) return;
-        void *hold = q->d_hist[q->cur], *hnew = q->d_hist[q->cur ^ 1];
+        void *hold = lq_hist_dev(&q->hist, q->ctx.stream), *hnew = lq_hist_next(&q->hist);
         const unsigned int HL = (q->p - 1) * q->M;
         if (HL) lqk_window_append(1, hold, HL, dx, nblocks * q->M, hnew, q->ctx.stream);
         lqk_firpfbch_analyzer(ctaps, q->M, q->p, q->d_hsub, hold, dx, nblocks, dy, q->ctx.stream);
-        if (HL) q->cur ^= 1;
+        lq_hist_flip(&q->hist);
     } else {
         void *z = lq_devbuf_get(&q->zbuf, (size_t)(q->p - 1 + nblocks) * q->M * 8);
         lqk_firpfbch_synthesizer(ctaps, q->M, q->p, q->d_hsub, q->d_zstate, z, dx, nblocks, dy, q->ctx.stream);

@@ -21,8 +21,7 @@ struct firpfbch2_crcf_s {
     float *h;          /* 2*M*m prototype taps */
     void *d_hsub;      /* M x 2m: hsub[i*2m + n] = h[i + n*M] */
     void *d_hsub_s;    /* analyzer: hsub / M (exact for M = 2^k), the fast path's form */
-    void *d_hist[2];   /* analyzer: last HL inputs */
-    int cur;
+    lq_hist hist;      /* analyzer: last HL inputs */
     void *d_zstate;    /* synthesizer: last 4m-1 IFFT vectors */
     int flag;          /* parity of the next block (reference `flag`) */
     lq_ctx ctx;
@@ -63,14 +62,12 @@ firpfbch2_crcf firpfbch2_crcf_create(int _type, unsigned int _M, unsigned int _m
         for (size_t i = 0; i < (size_t)_M * L; i++) hsub[i] *= inv;
         q->d_hsub_s = lqrt_malloc((size_t)_M * L * sizeof(float));
         lqrt_h2d(q->d_hsub_s, hsub, (size_t)_M * L * sizeof(float), q->ctx.stream);
-        q->d_hist[0] = lqrt_malloc((size_t)q->HL * 8);
-        q->d_hist[1] = lqrt_malloc((size_t)q->HL * 8);
+        lq_hist_init(&q->hist, q->HL, 8, LQ_HIST_DEV);
     } else {
         q->d_zstate = lqrt_malloc((size_t)(4 * _m - 1) * _M * 8);
     }
     lqrt_sync(q->ctx.stream);
     free(hsub);
-    q->cur = 0;
     q->flag = 0;
     return q;
 }
@@ -95,8 +92,7 @@ void firpfbch2_crcf_destroy(firpfbch2_crcf _q)
     lqrt_sync(_q->ctx.stream);
     lqrt_free(_q->d_hsub);
     lqrt_free(_q->d_hsub_s);
-    lqrt_free(_q->d_hist[0]);
-    lqrt_free(_q->d_hist[1]);
+    lq_hist_free(&_q->hist);   /* the analyzer's (never set up in a synthesizer: nothing to free) */
     lqrt_free(_q->d_zstate);
     lq_devbuf_free(&_q->xbuf);
     lq_devbuf_free(&_q->ybuf);
@@ -109,12 +105,11 @@ void firpfbch2_crcf_destroy(firpfbch2_crcf _q)
 void firpfbch2_crcf_reset(firpfbch2_crcf _q)
 {
     if (_q->type == LIQUID_ANALYZER) {
-        lqrt_memset(_q->d_hist[0], (size_t)_q->HL * 8, _q->ctx.stream);
-        lqrt_memset(_q->d_hist[1], (size_t)_q->HL * 8, _q->ctx.stream);
+        lq_hist_zero(&_q->hist, _q->ctx.stream);
     } else {
         lqrt_memset(_q->d_zstate, (size_t)(4 * _q->m - 1) * _q->M * 8, _q->ctx.stream);
+        lqrt_sync(_q->ctx.stream);
     }
-    lqrt_sync(_q->ctx.stream);
     _q->flag = 0;
 }
 
@@ -132,12 +127,12 @@ void firpfbch2_crcf_print(firpfbch2_crcf _q)
 static int firpfbch2_an_fast(firpfbch2_crcf _q, const void *_dx, unsigned long long _nblocks, void *_dy,
                              unsigned *flag, unsigned seq)
 {
-    void *hold = _q->d_hist[_q->cur], *hnew = _q->d_hist[_q->cur ^ 1];
+    void *hold = lq_hist_dev(&_q->hist, _q->ctx.stream), *hnew = lq_hist_next(&_q->hist);
     const lqk_hist_job job = {hold, _dx, _nblocks * (_q->M / 2), hnew, _q->HL};
     if (!lqk_firpfbch2_analyzer_fast(_q->M, _q->m, _q->d_hsub_s, hold, _dx, _nblocks, _q->flag, _dy, &job, flag, seq,
                                      _q->ctx.stream))
         return 0;
-    _q->cur ^= 1;
+    lq_hist_flip(&_q->hist);
     _q->flag = (int)((_q->flag + _nblocks) & 1);
     return 1;
 }
@@ -148,10 +143,10 @@ void firpfbch2_crcf_execute_block_dev(firpfbch2_crcf _q, const liquid_float_comp
     if (_nblocks == 0) return;
     if (_q->type == LIQUID_ANALYZER) {
         if (firpfbch2_an_fast(_q, _dx, _nblocks, _dy, NULL, 0)) return;
-        void *hold = _q->d_hist[_q->cur], *hnew = _q->d_hist[_q->cur ^ 1];
+        void *hold = lq_hist_dev(&_q->hist, _q->ctx.stream), *hnew = lq_hist_next(&_q->hist);
         lqk_firpfbch2_analyzer(_q->M, _q->m, _q->d_hsub, hold, _dx, _nblocks, _q->flag, _dy, _q->ctx.stream);
         lqk_window_append(1, hold, _q->HL, _dx, _nblocks * (_q->M / 2), hnew, _q->ctx.stream);
-        _q->cur ^= 1;
+        lq_hist_flip(&_q->hist);
     } else {
         size_t zb = (size_t)(4 * _q->m - 1 + _nblocks) * _q->M * 8;
         void *z = lq_devbuf_get(&_q->zbuf, zb);

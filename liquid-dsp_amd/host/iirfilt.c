@@ -255,7 +255,7 @@ static lq_iir *iir_new(int kind, const char *who)
 static void iir_finish(lq_iir *q)
 {
     const size_t ns = q->sos ? 2 * (size_t)q->nsos : (q->n > 2 ? q->n : 2);
-    lq_mirror_init(&q->sm, ns, q->sw * sizeof(float));
+    lq_mirror_init(&q->sm, ns, q->sw * sizeof(float), 0);
     device_form(q);
     if (q->dev_ok) q->d_state = lqrt_malloc((ns > 2 * q->nsec ? ns : 2 * q->nsec) * q->sw * sizeof(float));   /* zeroed */
 }

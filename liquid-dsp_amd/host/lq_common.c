@@ -238,6 +238,15 @@ void liquid_firdes_kaiser(unsigned int _n, float _fc, float _As, float _mu, floa
     lq_firdes_kaiser(_n, _fc, _As, _mu, _h);
 }
 
+float *lq_taps_from_real(int kind, float *hf, unsigned int n)
+{
+    if (kind != LQ_CCCF) return hf;
+    float *hc = (float *)lq_xmalloc((size_t)n * 2 * sizeof(float));   /* zeroed: imaginary parts 0 */
+    for (unsigned int i = 0; i < n; i++) hc[2 * i] = hf[i];
+    free(hf);
+    return hc;
+}
+
 /* ----------------------------------------------------------------- memory helpers (extension) */
 
 static void *g_default_stream = NULL;

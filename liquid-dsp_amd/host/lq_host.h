@@ -29,6 +29,11 @@
 /* sample kinds (also the kernel `kind` codes) */
 enum { LQ_RRRF = 0, LQ_CRCF = 1, LQ_CCCF = 2 };
 
+/* bytes per sample / per coefficient, and the type suffix of a kind */
+static inline size_t lq_esz(int kind) { return kind == LQ_RRRF ? 4 : 8; }
+static inline size_t lq_csz(int kind) { return kind == LQ_CCCF ? 8 : 4; }
+static inline const char *lq_ext(int kind) { return kind == LQ_RRRF ? "rrrf" : (kind == LQ_CRCF ? "crcf" : "cccf"); }
+
 /* grow-on-demand device buffer */
 typedef struct {
     void *p;
@@ -78,19 +83,83 @@ int lq_small_host(void);
 void lq_host_dot(int kind, const float *h, const void *x, unsigned int n, void *y);
 float *lq_host_taps(int kind, const float *h, unsigned int n, int rev);
 void lq_host_tdot(int kind, const float *g, const void *x, unsigned int n, void *y);
+/* y *= scale: a real scale per component (rrrf, crcf; firfilt.c:337), a
+ * complex one (cccf) */
+static inline void lq_host_scale(int kind, float sre, float sim, float *y)
+{
+    if (kind == LQ_CCCF) {
+        const float a = y[0], b = y[1];
+        y[0] = a * sre - b * sim;
+        y[1] = a * sim + b * sre;
+        return;
+    }
+    y[0] *= sre;
+    if (kind == LQ_CRCF) y[1] *= sre;
+}
+/* real design taps in a kind's coefficient layout: hf itself, or for cccf
+ * its (h, 0) pairs with hf freed; the caller frees the result */
+float *lq_taps_from_real(int kind, float *hf, unsigned int n);
+
+/* host copy of a device-resident history of n samples; pinned: the buffer is
+ * pinned host memory, which a kernel may read in place */
 typedef struct {
     unsigned char *buf;
     size_t n, esz, cap, off;   /* history = n samples at buf + off*esz */
+    int pinned;
     int host_valid, dev_valid;
 } lq_mirror;
-void lq_mirror_init(lq_mirror *m, size_t n, size_t esz);
+void lq_mirror_init(lq_mirror *m, size_t n, size_t esz, int pinned);
 void lq_mirror_free(lq_mirror *m);
 void lq_mirror_zero(lq_mirror *m);
 void lq_mirror_need_host(lq_mirror *m, const void *dev_hist, void *stream);
 void lq_mirror_need_dev(lq_mirror *m, void *dev_hist, void *stream);
 void lq_mirror_append(lq_mirror *m, const void *x, size_t k);
-void lq_mirror_commit(lq_mirror *m, size_t k);
-unsigned char *lq_mirror_ptr(lq_mirror *m);
+/* after an append of k samples: keep the last n */
+static inline void lq_mirror_commit(lq_mirror *m, size_t k) { m->off += k; }
+static inline unsigned char *lq_mirror_ptr(lq_mirror *m) { return m->buf + m->off * m->esz; }
+
+/* The streaming history of an object (host/lq_hist.c): the last n samples,
+ * oldest first, in two device buffers used ping-pong -- a block call reads
+ * the current one, its kernel (or lqk_window_append) writes the other, and
+ * lq_hist_flip makes that one current -- plus, by mode, a host mirror for
+ * the calls that compute on the host (MIRROR), in pinned memory where the
+ * single-output kernels read the window in place (PINNED).  Whichever side
+ * ran last is authoritative; the other is refreshed on demand.  n may be 0. */
+enum { LQ_HIST_DEV = 0, LQ_HIST_MIRROR = 1, LQ_HIST_PINNED = 2 };
+typedef struct {
+    void *d[2];
+    int cur, mode;
+    lq_mirror m;
+} lq_hist;
+void lq_hist_init(lq_hist *h, size_t n, size_t esz, int mode);
+void lq_hist_free(lq_hist *h);
+void lq_hist_zero(lq_hist *h, void *stream);   /* both sides zero and in step; waits for the stream */
+void *lq_hist_dev(lq_hist *h, void *stream);   /* the current device buffer, brought up to date */
+const void *lq_hist_read(lq_hist *h);          /* the window where it is authoritative: the device
+                                                  buffer, or (PINNED) the host window after appends */
+static inline void *lq_hist_next(lq_hist *h) { return h->d[h->cur ^ 1]; }
+/* after the launch that wrote lq_hist_next: it is current, the host copy stale */
+static inline void lq_hist_flip(lq_hist *h)
+{
+    h->cur ^= 1;
+    h->m.host_valid = 0;
+}
+/* host side: the window of n samples, up to date (after a device block this
+ * waits for the device) */
+static inline unsigned char *lq_hist_host(lq_hist *h, void *stream)
+{
+    if (!h->m.host_valid) lq_mirror_need_host(&h->m, h->d[h->cur], stream);
+    return lq_mirror_ptr(&h->m);
+}
+/* ... with k samples appended: n + k samples, newest last; lq_hist_commit
+ * then keeps the last n */
+static inline unsigned char *lq_hist_append(lq_hist *h, const void *x, size_t k, void *stream)
+{
+    lq_hist_host(h, stream);
+    lq_mirror_append(&h->m, x, k);
+    return lq_mirror_ptr(&h->m);
+}
+static inline void lq_hist_commit(lq_hist *h, size_t k) { lq_mirror_commit(&h->m, k); }
 
 void *lq_xmalloc(size_t bytes);
 unsigned int lq_msb_index(unsigned int x);

@@ -213,29 +213,36 @@ void lq_host_tdot(int kind, const float *g, const void *x, unsigned int n, void 
 }
 
 /* ------------------------------------------------------------------ mirrors
- * A host copy of a device-resident history of n samples (double-buffered on
- * the device: the current buffer is passed in).  Whichever side ran last is
- * authoritative; the other is refreshed on demand. */
-void lq_mirror_init(lq_mirror *m, size_t n, size_t esz)
+ * A host copy of a device-resident history of n samples (the host half of
+ * lq_hist; the device buffer is passed in).  Whichever side ran last is
+ * authoritative; the other is refreshed on demand.  The buffer has room for
+ * n + 64 appended samples before the window moves back to its start. */
+static unsigned char *lq_mirror_alloc(const lq_mirror *m, size_t cap)
+{
+    const size_t bytes = (cap ? cap : 1) * m->esz;
+    return (unsigned char *)(m->pinned ? lqrt_host_alloc(bytes) : lq_xmalloc(bytes));
+}
+
+void lq_mirror_init(lq_mirror *m, size_t n, size_t esz, int pinned)
 {
     m->n = n;
     m->esz = esz;
-    m->cap = 2 * n + 64;   /* room to append before compacting */
-    m->buf = (unsigned char *)lq_xmalloc((m->cap ? m->cap : 1) * esz);
-    memset(m->buf, 0, (m->cap ? m->cap : 1) * esz);
-    m->off = 0;
-    m->host_valid = m->dev_valid = 1;
+    m->pinned = pinned;
+    m->cap = 2 * n + 64;
+    m->buf = lq_mirror_alloc(m, m->cap);
+    lq_mirror_zero(m);
 }
 
 void lq_mirror_free(lq_mirror *m)
 {
-    free(m->buf);
+    if (m->pinned) lqrt_host_free(m->buf);
+    else free(m->buf);
     m->buf = NULL;
 }
 
 void lq_mirror_zero(lq_mirror *m)
 {
-    memset(m->buf, 0, (m->cap ? m->cap : 1) * m->esz);
+    memset(m->buf, 0, m->n * m->esz);
     m->off = 0;
     m->host_valid = m->dev_valid = 1;
 }
@@ -264,12 +271,11 @@ void lq_mirror_append(lq_mirror *m, const void *x, size_t k)
 {
     if (m->off + m->n + k > m->cap) {
         if (m->n + k > m->cap) {
-            const size_t cap = 2 * (m->n + k) + 64;
-            unsigned char *b = (unsigned char *)lq_xmalloc(cap * m->esz);
-            memcpy(b, m->buf + m->off * m->esz, m->n * m->esz);
-            free(m->buf);
-            m->buf = b;
-            m->cap = cap;
+            lq_mirror old = *m;
+            m->cap = 2 * (m->n + k) + 64;
+            m->buf = lq_mirror_alloc(m, m->cap);
+            memcpy(m->buf, lq_mirror_ptr(&old), m->n * m->esz);
+            lq_mirror_free(&old);
         } else {
             memmove(m->buf, m->buf + m->off * m->esz, m->n * m->esz);
         }
@@ -278,8 +284,3 @@ void lq_mirror_append(lq_mirror *m, const void *x, size_t k)
     memcpy(m->buf + (m->off + m->n) * m->esz, x, k * m->esz);
     m->dev_valid = 0;
 }
-
-/* after an append of k samples: keep the last n */
-void lq_mirror_commit(lq_mirror *m, size_t k) { m->off += k; }
-
-unsigned char *lq_mirror_ptr(lq_mirror *m) { return m->buf + m->off * m->esz; }

@@ -79,18 +79,15 @@ struct lq_rs_s {
     int rate_changed;             /* set_rate / adjust_rate since the last plan */
     unsigned long long gpos;      /* inputs consumed since the plan origin */
     rs_state now;                 /* timing state at gpos */
-    void *d_hist[2];              /* last L inputs */
-    int cur;
+    lq_hist hist;                 /* last L inputs; mirrored for the small-call mode */
     float *hbank;                 /* host bank taps h[b + n*npfb], n < L, reversed and expanded (lq_host_taps), hbs floats per bank */
     size_t hbs;
-    lq_mirror hm;                 /* host copy of the history (small-call mode) */
     rs_state hs;                  /* timing state of the host path, valid while hs_valid */
     int hs_valid;
     lq_ctx ctx;
     lq_devbuf xbuf, ybuf, ubuf;   /* ubuf: resampler outputs of an unfused chain chunk */
 };
 
-static const char *lq_ext[] = {"rrrf", "crcf", "cccf"};
 
 static const rs_state rs_initial = {0.0f, 0.0f, 0, RS_INTERP};   /* resamp.c:181-195 */
 
@@ -595,14 +592,14 @@ static void rs_plan_build_direct(lq_rs *q, unsigned long long nx)
      * records an input plan instead) */
     rs_rec_init(&q->pl.rec, rs_d4_shape(q) ? RS_D4 : RS_D3, rs_p2(q), rs_d4_shape(q) ? RS_D4_MAXOUT / 4 : (size_t)-1);
     if (rs_walk(q, q->now, nx, 0, &q0, &Kend, &lam, &q->pl.rec) != nx || Kend > 0xffffffffull)
-        LQ_FAIL("error: resamp_%s: too many outputs for one call\n", lq_ext[q->kind]);
+        LQ_FAIL("error: resamp_%s: too many outputs for one call\n", lq_ext(q->kind));
     q->pl.pre = nx + 1;
     q->pl.P = 1;
     q->pl.Q = 0;
     q->pl.end = nx;
     q->pl.origin = q->now;
     q->pl.periodic = 0;
-    if (!rs_plan_device(q, 1)) LQ_FAIL("error: resamp_%s: timing plan\n", lq_ext[q->kind]);
+    if (!rs_plan_device(q, 1)) LQ_FAIL("error: resamp_%s: timing plan\n", lq_ext(q->kind));
     q->pl.valid = 1;
     q->gpos = 0;
 }
@@ -610,7 +607,7 @@ static void rs_plan_build_direct(lq_rs *q, unsigned long long nx)
 static void rs_check_rate(lq_rs *q)
 {
     if (!(q->del > 0.0f) || isinf(q->del) || isnan(q->del))
-        LQ_FAIL("error: resamp_%s_execute(), invalid resampling rate (%f)\n", lq_ext[q->kind], q->rate);
+        LQ_FAIL("error: resamp_%s_execute(), invalid resampling rate (%f)\n", lq_ext(q->kind), q->rate);
 }
 
 /* make the plan cover inputs [gpos, gpos + nx); returns how many of them it covers */
@@ -664,16 +661,16 @@ static void rs_sync_now(lq_rs *q)
 
 lq_rs *lq_rs_create(int kind, float _rate, unsigned int _m, float _fc, float _As, unsigned int _npfb)
 {
-    if (_rate <= 0) LQ_FAIL("error: resamp_%s_create(), resampling rate must be greater than zero\n", lq_ext[kind]);
-    if (_m == 0) LQ_FAIL("error: resamp_%s_create(), filter semi-length must be greater than zero\n", lq_ext[kind]);
-    if (_npfb == 0) LQ_FAIL("error: resamp_%s_create(), number of filter banks must be greater than zero\n", lq_ext[kind]);
-    if (_fc <= 0.0f || _fc >= 0.5f) LQ_FAIL("error: resamp_%s_create(), filter cutoff must be in (0,0.5)\n", lq_ext[kind]);
+    if (_rate <= 0) LQ_FAIL("error: resamp_%s_create(), resampling rate must be greater than zero\n", lq_ext(kind));
+    if (_m == 0) LQ_FAIL("error: resamp_%s_create(), filter semi-length must be greater than zero\n", lq_ext(kind));
+    if (_npfb == 0) LQ_FAIL("error: resamp_%s_create(), number of filter banks must be greater than zero\n", lq_ext(kind));
+    if (_fc <= 0.0f || _fc >= 0.5f) LQ_FAIL("error: resamp_%s_create(), filter cutoff must be in (0,0.5)\n", lq_ext(kind));
     if (_As <= 0.0f)
-        LQ_FAIL("error: resamp_%s_create(), filter stop-band suppression must be greater than zero\n", lq_ext[kind]);
+        LQ_FAIL("error: resamp_%s_create(), filter stop-band suppression must be greater than zero\n", lq_ext(kind));
     lqrt_require_device("resamp_create");
     lq_rs *q = (lq_rs *)lq_xmalloc(sizeof(*q));
     q->kind = kind;
-    q->esz = kind == LQ_RRRF ? 4 : 8;
+    q->esz = lq_esz(kind);
     q->rate = _rate;
     q->del = 1.0f / _rate;
     q->m = _m;
@@ -714,9 +711,7 @@ lq_rs *lq_rs_create(int kind, float _rate, unsigned int _m, float _fc, float _As
     lqrt_h2d(q->d_taps, tp, ntap * 2 * sizeof(float), q->ctx.stream);
     q->d_taps2 = lqrt_malloc(ntap2 * 2 * sizeof(float));
     lqrt_h2d(q->d_taps2, tp2, ntap2 * 2 * sizeof(float), q->ctx.stream);
-    q->d_hist[0] = lqrt_malloc((size_t)q->L * q->esz);
-    q->d_hist[1] = lqrt_malloc((size_t)q->L * q->esz);
-    lqrt_sync(q->ctx.stream);
+    lq_hist_init(&q->hist, q->L, q->esz, LQ_HIST_MIRROR);
     lqrt_sync(q->ctx.stream);
     {
         const int ck = q->kind == LQ_RRRF ? LQ_RRRF : LQ_CRCF;   /* real taps for every type */
@@ -731,7 +726,6 @@ lq_rs *lq_rs_create(int kind, float _rate, unsigned int _m, float _fc, float _As
         }
         free(hb);
     }
-    lq_mirror_init(&q->hm, q->L, q->esz);
     q->hs_valid = 0;
     free(tp);
     free(tp2);
@@ -746,14 +740,12 @@ void lq_rs_destroy(lq_rs *_q)
     lqrt_sync(_q->ctx.stream);
     lqrt_free(_q->d_taps);
     lqrt_free(_q->d_taps2);
-    lqrt_free(_q->d_hist[0]);
-    lqrt_free(_q->d_hist[1]);
+    lq_hist_free(&_q->hist);
     lq_devbuf_free(&_q->pl.d_tab);
     lq_devbuf_free(&_q->xbuf);
     lq_devbuf_free(&_q->ybuf);
     lq_devbuf_free(&_q->ubuf);
     lq_ctx_free(&_q->ctx);
-    lq_mirror_free(&_q->hm);
     free(_q->hbank);
     free(_q->pl.tab);
     rs_rec_free(&_q->pl.rec);
@@ -769,10 +761,7 @@ static void lq_rs_print(lq_rs *_q)
 
 void lq_rs_reset(lq_rs *_q)
 {
-    lqrt_memset(_q->d_hist[0], (size_t)_q->L * _q->esz, _q->ctx.stream);
-    lqrt_memset(_q->d_hist[1], (size_t)_q->L * _q->esz, _q->ctx.stream);
-    lqrt_sync(_q->ctx.stream);
-    lq_mirror_zero(&_q->hm);
+    lq_hist_zero(&_q->hist, _q->ctx.stream);
     _q->hs_valid = 0;
     _q->now = rs_initial;
     _q->gpos = 0;
@@ -795,7 +784,7 @@ static void rs_new_del(lq_rs *q, float del)
 
 static void lq_rs_set_rate(lq_rs *_q, float _rate)
 {
-    if (_rate <= 0) LQ_FAIL("error: resamp_%s_set_rate(), resampling rate must be greater than zero\n", lq_ext[_q->kind]);
+    if (_rate <= 0) LQ_FAIL("error: resamp_%s_set_rate(), resampling rate must be greater than zero\n", lq_ext(_q->kind));
     _q->rate = _rate;
     rs_new_del(_q, 1.0f / _q->rate);
 }
@@ -804,7 +793,7 @@ static void lq_rs_set_rate(lq_rs *_q, float _rate)
 static void lq_rs_adjust_rate(lq_rs *_q, float _delta)
 {
     if (_delta > 0.1f || _delta < -0.1f)
-        LQ_FAIL("error: resamp_%s_adjust_rate(), resampling rate must be in [-0.1,0.1]\n", lq_ext[_q->kind]);
+        LQ_FAIL("error: resamp_%s_adjust_rate(), resampling rate must be in [-0.1,0.1]\n", lq_ext(_q->kind));
     _q->rate += _delta;
     if (_q->rate > 0.5f) _q->rate = 0.5f;
     if (_q->rate < -0.5f) _q->rate = -0.5f;
@@ -846,8 +835,6 @@ void lq_rs_block_dev_hb(lq_rs *_q, const void *_dxv, unsigned long long _nx, voi
     const char *_dx = (const char *)_dxv;
     char *_dy = (char *)_dyv;
     unsigned long long total = 0;
-    lq_mirror_need_dev(&_q->hm, _q->d_hist[_q->cur], _q->ctx.stream);
-    _q->hm.host_valid = 0;
     _q->hs_valid = 0;
     /* launches of at most LQK_RS_MAXN inputs and 2^27 outputs (32-bit
      * buffer offsets in the kernel) */
@@ -856,7 +843,7 @@ void lq_rs_block_dev_hb(lq_rs *_q, const void *_dxv, unsigned long long _nx, voi
     while (_nx > 0) {
         unsigned long long c = rs_ensure_plan(_q, _nx < cmax ? _nx : cmax);
         unsigned long long K0 = rs_K(_q, _q->gpos), K1 = rs_K(_q, _q->gpos + c);
-        void *hold = _q->d_hist[_q->cur], *hnew = _q->d_hist[_q->cur ^ 1];
+        void *hold = lq_hist_dev(&_q->hist, _q->ctx.stream), *hnew = lq_hist_next(&_q->hist);
         const unsigned long long nk = K1 - K0;
         const int fuse = hb && nk > 0 && _q->pl.dk == RS_D4 && lqk_resamp4_hb_supported(_q->npfb, _q->L, _q->del, hb->m);
         /* an unfused chain chunk: the resampler's outputs through ubuf */
@@ -884,7 +871,7 @@ void lq_rs_block_dev_hb(lq_rs *_q, const void *_dxv, unsigned long long _nx, voi
         }
         if (hb && !fuse && nk > 0) hb->run(hb->ctx, uy, nk, _dy);
         if (_q->pl.dk != RS_D4) lqk_window_append(_q->kind != LQ_RRRF, hold, _q->L, _dx, c, hnew, _q->ctx.stream);
-        _q->cur ^= 1;
+        lq_hist_flip(&_q->hist);
         _q->gpos += c;
         _dx += c * _q->esz;
         _dy += (hb ? 2 : 1) * nk * _q->esz;
@@ -910,9 +897,7 @@ static void lq_rs_exec1_host(lq_rs *q, const void *x, void *y, unsigned int *ny)
         }
         q->hs_valid = 1;
     }
-    lq_mirror_need_host(&q->hm, q->d_hist[q->cur], q->ctx.stream);
-    lq_mirror_append(&q->hm, x, 1);
-    const unsigned char *w = lq_mirror_ptr(&q->hm);   /* L + 1 samples, x last */
+    const unsigned char *w = lq_hist_append(&q->hist, x, 1, q->ctx.stream);   /* L + 1 samples, x last */
     const int ck = q->kind == LQ_RRRF ? LQ_RRRF : LQ_CRCF;   /* real taps for every type */
     const unsigned int L = q->L, npfb = q->npfb;
     const int np = (int)npfb;
@@ -946,7 +931,7 @@ static void lq_rs_exec1_host(lq_rs *q, const void *x, void *y, unsigned int *ny)
     }
     s->tau -= 1.0f;
     s->b = (int)((unsigned int)s->b - npfb);
-    lq_mirror_commit(&q->hm, 1);
+    lq_hist_commit(&q->hist, 1);
     /* the device path continues from here: its plan position, or its state */
     if (q->pl.valid && (q->pl.periodic || q->gpos + 1 <= q->pl.end)) q->gpos += 1;
     else q->pl.valid = 0;

@@ -21,7 +21,6 @@
 
 #include "lq_host.h"
 
-static const char *lq_ext[] = {"rrrf", "crcf", "cccf"};
 
 /* ===================================================================== resamp2 */
 typedef struct {
@@ -62,9 +61,9 @@ static void lq_r2_design(lq_r2 *q)
 
 static lq_r2 *lq_r2_create(int kind, unsigned int m, float f0, float As)
 {
-    if (m < 2) LQ_FAIL("error: resamp2_%s_create(), filter semi-length must be at least 2\n", lq_ext[kind]);
+    if (m < 2) LQ_FAIL("error: resamp2_%s_create(), filter semi-length must be at least 2\n", lq_ext(kind));
     if (f0 < -0.5f || f0 > 0.5f)
-        LQ_FAIL("error: resamp2_%s_create(), f0 (%12.4e) must be in (-1,1)\n", lq_ext[kind], f0);
+        LQ_FAIL("error: resamp2_%s_create(), f0 (%12.4e) must be in (-1,1)\n", lq_ext(kind), f0);
     lqrt_require_device("resamp2_create");
     lq_r2 *q = (lq_r2 *)lq_xmalloc(sizeof(*q));
     q->kind = kind;
@@ -248,7 +247,7 @@ static void lq_ms2_set_stream(lq_ms2 *q, void *s)
 
 static lq_ms2 *lq_ms2_create(int kind, int type, unsigned int ns, float fc, float f0, float As)
 {
-    const char *e = lq_ext[kind];
+    const char *e = lq_ext(kind);
     if (ns > 16) LQ_FAIL("error: msresamp2_%s_create(), number of stages should not exceed 16\n", e);
     if (fc <= 0.0f || fc >= 0.5f) LQ_FAIL("error: msresamp2_%s_create(), cut-off frequency must be in (0,0.5)\n", e);
     if (fc > 0.45f) {
@@ -422,7 +421,7 @@ static void lq_ms_set_stream(lq_ms *q, void *s)
 
 static lq_ms *lq_ms_create(int kind, float r, float As)
 {
-    if (r <= 0.0f) LQ_FAIL("error: msresamp_%s_create(), resampling rate must be greater than zero\n", lq_ext[kind]);
+    if (r <= 0.0f) LQ_FAIL("error: msresamp_%s_create(), resampling rate must be greater than zero\n", lq_ext(kind));
     lq_ms *q = (lq_ms *)lq_xmalloc(sizeof(*q));
     q->kind = kind;
     q->esz = kind == LQ_RRRF ? 4 : 8;

@@ -26,8 +26,7 @@ typedef struct {
     unsigned int nfft, W;
     float *w;                 /* host copy of the scaled window */
     float *d_w;
-    void *d_hist[2];          /* last W inputs */
-    int cur;
+    lq_hist hist;             /* last W inputs */
     float *d_psd;             /* accumulated psd (natural order) */
     unsigned int sample_counter, num_transforms;
     unsigned char *pend;      /* push()/write() samples not yet on the device */
@@ -36,6 +35,8 @@ typedef struct {
     lq_ctx ctx;
     lq_devbuf xbuf, Xbuf, ends, acc, out, work;
 } lq_spg;
+
+static void *lq_spg_win(lq_spg *q) { return lq_hist_dev(&q->hist, q->ctx.stream); }   /* the current window */
 
 static lq_spg *lq_spg_create(int real_in, unsigned int nfft, const float *window, unsigned int W, const char *who)
 {
@@ -57,8 +58,7 @@ static lq_spg *lq_spg_create(int real_in, unsigned int nfft, const float *window
     lq_ctx_init(&q->ctx);
     q->d_w = (float *)lqrt_malloc(W * sizeof(float));
     lqrt_h2d(q->d_w, q->w, W * sizeof(float), q->ctx.stream);
-    q->d_hist[0] = lqrt_malloc((size_t)W * q->esz);
-    q->d_hist[1] = lqrt_malloc((size_t)W * q->esz);
+    lq_hist_init(&q->hist, W, q->esz, LQ_HIST_DEV);
     q->d_psd = (float *)lqrt_malloc(nfft * sizeof(float));
     q->plan = fft_create_plan(nfft, NULL, NULL, LIQUID_FFT_FORWARD, 0);
     fft_set_stream(q->plan, q->ctx.stream);
@@ -67,11 +67,10 @@ static lq_spg *lq_spg_create(int real_in, unsigned int nfft, const float *window
 
 static void lq_spg_reset(lq_spg *q)
 {
-    lqrt_memset(q->d_hist[q->cur], (size_t)q->W * q->esz, q->ctx.stream);
     float *ones = (float *)lq_xmalloc(q->nfft * sizeof(float));
     for (unsigned int i = 0; i < q->nfft; i++) ones[i] = 1.0f;
     lqrt_h2d(q->d_psd, ones, q->nfft * sizeof(float), q->ctx.stream);
-    lqrt_sync(q->ctx.stream);
+    lq_hist_zero(&q->hist, q->ctx.stream);   /* waits for the stream: ones is done with */
     free(ones);
     q->npend = 0;
     q->num_transforms = 0;
@@ -83,8 +82,7 @@ static void lq_spg_destroy(lq_spg *q)
     lqrt_sync(q->ctx.stream);
     fft_destroy_plan(q->plan);
     lqrt_free(q->d_w);
-    lqrt_free(q->d_hist[0]);
-    lqrt_free(q->d_hist[1]);
+    lq_hist_free(&q->hist);
     lqrt_free(q->d_psd);
     lq_devbuf_free(&q->xbuf);
     lq_devbuf_free(&q->Xbuf);
@@ -117,8 +115,8 @@ static void lq_spg_stage(lq_spg *q, const void *x, size_t n)
 static void lq_spg_append_dev(lq_spg *q, const void *dx, unsigned long long n)
 {
     if (n == 0) return;
-    lqk_window_append(!q->real_in, q->d_hist[q->cur], q->W, dx, n, q->d_hist[q->cur ^ 1], q->ctx.stream);
-    q->cur ^= 1;
+    lqk_window_append(!q->real_in, lq_spg_win(q), q->W, dx, n, lq_hist_next(&q->hist), q->ctx.stream);
+    lq_hist_flip(&q->hist);
 }
 
 static void lq_spg_flush(lq_spg *q)
@@ -144,7 +142,7 @@ static void lq_spg_transforms(lq_spg *q, const void *dx, const long long *ends, 
         long long *de = (long long *)lq_devbuf_get(&q->ends, nb * sizeof(long long));
         lqrt_h2d(de, ends + t0, nb * sizeof(long long), q->ctx.stream);
         void *X = lq_devbuf_get(&q->Xbuf, (size_t)nb * q->nfft * 8);
-        lqk_spgram_gather(q->real_in, q->d_hist[q->cur], q->W, dx, de, nb, q->d_w, q->nfft, X, q->ctx.stream);
+        lqk_spgram_gather(q->real_in, lq_spg_win(q), q->W, dx, de, nb, q->d_w, q->nfft, X, q->ctx.stream);
         fft_execute_batch_dev(q->plan, X, X, nb);
         each(q, X, nb, arg);
         lqrt_sync(q->ctx.stream);   /* ends/X buffers are reused by the next batch */
@@ -159,7 +157,7 @@ static void *lq_spg_execute_dev(lq_spg *q)
     long long *de = (long long *)lq_devbuf_get(&q->ends, sizeof(long long));
     lqrt_h2d(de, &e, sizeof(e), q->ctx.stream);
     void *X = lq_devbuf_get(&q->Xbuf, (size_t)q->nfft * 8);
-    lqk_spgram_gather(q->real_in, q->d_hist[q->cur], q->W, NULL, de, 1, q->d_w, q->nfft, X, q->ctx.stream);
+    lqk_spgram_gather(q->real_in, lq_spg_win(q), q->W, NULL, de, 1, q->d_w, q->nfft, X, q->ctx.stream);
     fft_execute_batch_dev(q->plan, X, X, 1);
     return X;
 }
@@ -201,7 +199,7 @@ static void lq_spg_accumulate_dev(lq_spg *q, const void *dx, unsigned long long 
             if (T > 0) {
                 float a = q->num_transforms == 0 ? 1.0f : alpha;
                 void *w = lq_devbuf_get(&q->work, lqk_spgram_work_bytes(T, q->nfft));
-                lqk_spgram_fused1024(q->real_in, q->d_hist[q->cur], q->W, dx, first, (long long)H, T,
+                lqk_spgram_fused1024(q->real_in, lq_spg_win(q), q->W, dx, first, (long long)H, T,
                                      first + (long long)((T - 1) * H), q->d_w, 1, a, q->d_psd, w, q->ctx.stream);
                 q->num_transforms += (unsigned int)T;
             }
@@ -254,7 +252,7 @@ static void lq_spg_estimate_dev(lq_spg *q, const void *dx, unsigned long long n,
     lqrt_memset(acc, q->nfft * sizeof(float), q->ctx.stream);
     if (q->nfft == 1024 && n < (1ull << 27)) {   /* fused path: ends are delay-1 + t delay, the last one n-1 */
         void *w = lq_devbuf_get(&q->work, lqk_spgram_work_bytes(T, q->nfft));
-        lqk_spgram_fused1024(q->real_in, q->d_hist[q->cur], q->W, dx, (long long)delay - 1, (long long)delay, T,
+        lqk_spgram_fused1024(q->real_in, lq_spg_win(q), q->W, dx, (long long)delay - 1, (long long)delay, T,
                              (long long)n - 1, q->d_w, 0, 0.0f, acc, w, q->ctx.stream);
         lqk_spgram_db(2, NULL, acc, q->nfft, (float)T, dpsd, q->ctx.stream);
         lq_spg_append_dev(q, dx, n);

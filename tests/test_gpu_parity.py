@@ -847,6 +847,52 @@ def test_firpfb_block_and_push_vs_oracle(M, hlen, t):
     assert G.nrm_err(y2, ref[2010:]) < NRM
 
 
+# -------------------------------------------- per-sample calls on the pinned window
+# push() appends to the pinned host window, which moves back to the start of
+# its buffer every n + 64 pushes (n = the window length, at most 128 here), and
+# the single-output kernels read it in place; block calls in between hand the
+# window to the device and back.
+@pytest.mark.parametrize("t", ["rrrf", "crcf", "cccf"])
+@pytest.mark.parametrize("hlen", [1, 13, 40, 100])
+def test_firfilt_push_execute_across_window_moves(t, hlen):
+    r = rng(hlen * 5 + 1)
+    h = coefs(r, t, hlen)
+    x = samples(r, t, 1600)
+    g = LQ.FirFilt(t, h)
+    out = []
+    for a, b, per in [(0, 100, False), (100, 1100, True), (1100, 1300, False), (1300, 1600, True)]:
+        if per:
+            for v in x[a:b]:
+                g.push(v)
+                out.append(np.atleast_1d(g.execute()))
+        else:
+            out.append(g.execute_block(x[a:b]))
+    assert G.nrm_err(np.concatenate(out), O.FirFilt(TYPES[t], h).execute_block(x)) < NRM
+
+
+@pytest.mark.parametrize("t", ["rrrf", "crcf", "cccf"])
+@pytest.mark.parametrize("M,hlen", [(5, 7), (8, 64), (32, 449)])
+def test_firpfb_push_execute_across_window_moves(M, hlen, t):
+    r = rng(M * 7 + hlen)
+    h = coefs(r, t, hlen)
+    x = samples(r, t, 700)
+    g = LQ.FirPfb(M, h, t=t)
+    o = O.FirPfb(TYPES[t], M, h)
+    ref = np.empty((len(x), M), np.float32 if t == "rrrf" else np.complex64)
+    for k, v in enumerate(x):
+        o.push(v)
+        ref[k] = [o.execute(i) for i in range(M)]
+    y1 = np.asarray(g.execute_block(x[:200])).reshape(-1, M)
+    per = []
+    for k in range(200, 600):           # one bank per push, cycling through the banks
+        g.push(x[k])
+        per.append(g.execute(k % M))
+    y2 = np.asarray(g.execute_block(x[600:])).reshape(-1, M)
+    assert G.nrm_err(y1, ref[:200]) < NRM
+    assert G.nrm_err(np.array(per), ref[np.arange(200, 600), np.arange(200, 600) % M]) < NRM
+    assert G.nrm_err(y2, ref[600:]) < NRM
+
+
 # ------------------------------------------------------------ prototype constructors
 # *_create_rnyquist / *_create_prototype design taps on the host
 # (liquid_firdes_prototype, pinned in tests/test_firdes.py) and hand them to

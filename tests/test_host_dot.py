@@ -35,8 +35,9 @@ def test_host_tdot_matches_float64(kind, rev):
             h = (rng.standard_normal(n) + 1j * rng.standard_normal(n)).astype(np.complex64)
         else:
             h = rng.standard_normal(n).astype(np.float32)
-        # one sample into a larger array: the 16-byte and 32-byte load forms
-        # (lq_host_tdot picks by the samples' alignment) both run
+        # one sample into a larger array, so both alignments are read; the
+        # 16-byte and 32-byte load forms (lq_host_tdot picks by the length
+        # and AVX2 support) both run over the lengths above
         off = n % 2
         if kind == "rrrf":
             x = rng.standard_normal(n + 1).astype(np.float32)[off:off + n]
