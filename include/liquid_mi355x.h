@@ -497,8 +497,25 @@ void firhilbf_synchronize(firhilbf _q);
    divided by _a[0]; direct form II), create_sos (a cascade of second-order
    sections, 3 coefficients each), and the ready-made DC blocker, PLL loop
    filter, integrator and differentiator.  create_prototype and
-   create_lowpass (the Butterworth / Chebyshev / elliptic / Bessel designs)
-   are not part of this library yet and are deliberately not declared. */
+   create_lowpass are deliberately not declared: design the coefficients with
+   liquid_iirdes (below) and pass them to create_sos (SOS format) or create
+   (TF format).  A TF design of order above 2, and a cascade of more than 8
+   sections, run in the host loop. */
+typedef enum {
+    LIQUID_IIRDES_BUTTER = 0,
+    LIQUID_IIRDES_CHEBY1,
+    LIQUID_IIRDES_CHEBY2,
+    LIQUID_IIRDES_ELLIP,
+    LIQUID_IIRDES_BESSEL
+} liquid_iirdes_filtertype;
+typedef enum {
+    LIQUID_IIRDES_LOWPASS = 0,
+    LIQUID_IIRDES_HIGHPASS,
+    LIQUID_IIRDES_BANDPASS,
+    LIQUID_IIRDES_BANDSTOP
+} liquid_iirdes_bandtype;
+typedef enum { LIQUID_IIRDES_SOS = 0, LIQUID_IIRDES_TF } liquid_iirdes_format;
+
 #define LQMI_IIRFILT_API(IIRFILT, TO, TC, TI)                                                   \
     typedef struct IIRFILT##_s *IIRFILT;                                                        \
     IIRFILT IIRFILT##_create(TC *_b, unsigned int _nb, TC *_a, unsigned int _na);               \
@@ -533,11 +550,91 @@ void iirdes_dzpk2sosf(liquid_float_complex *_zd, liquid_float_complex *_pd, unsi
                       liquid_float_complex _kd, float *_B, float *_A);
 void iirdes_pll_active_lag(float _w, float _zeta, float _K, float *_b, float *_a);
 void iirdes_pll_active_PI(float _w, float _zeta, float _K, float *_b, float *_a);
+
+/* Recursive filter design (liquid.h:1688-1880; host code, no GPU).
+   liquid_iirdes: _n the order of the low-pass prototype, _fc its cut-off,
+   _f0 the centre frequency of a band-pass or band-stop design (whose order is
+   2 _n), _Ap / _As the pass-band ripple and stop-band attenuation [dB] where
+   the type has one.  _B, _A: 3 coefficients per section, ceil(order / 2)
+   sections (SOS), or order + 1 coefficients each (TF). */
+void liquid_iirdes(liquid_iirdes_filtertype _ftype, liquid_iirdes_bandtype _btype, liquid_iirdes_format _format,
+                   unsigned int _n, float _fc, float _f0, float _Ap, float _As, float *_B, float *_A);
+/* analog low-pass prototypes: zeros, poles (conjugate pairs together, the real
+   pole of an odd order last) and gain */
+void butter_azpkf(unsigned int _n, liquid_float_complex *_za, liquid_float_complex *_pa, liquid_float_complex *_ka);
+void cheby1_azpkf(unsigned int _n, float _ep, liquid_float_complex *_z, liquid_float_complex *_p,
+                  liquid_float_complex *_k);
+void cheby2_azpkf(unsigned int _n, float _es, liquid_float_complex *_z, liquid_float_complex *_p,
+                  liquid_float_complex *_k);
+void ellip_azpkf(unsigned int _n, float _ep, float _es, liquid_float_complex *_z, liquid_float_complex *_p,
+                 liquid_float_complex *_k);
+void bessel_azpkf(unsigned int _n, liquid_float_complex *_z, liquid_float_complex *_p, liquid_float_complex *_k);
+/* transforms between the analog and digital planes and between forms */
+float iirdes_freqprewarp(liquid_iirdes_bandtype _btype, float _fc, float _f0);
+void bilinear_zpkf(liquid_float_complex *_za, unsigned int _nza, liquid_float_complex *_pa, unsigned int _npa,
+                   liquid_float_complex _ka, float _m, liquid_float_complex *_zd, liquid_float_complex *_pd,
+                   liquid_float_complex *_kd);
+void iirdes_dzpk_lp2hp(liquid_float_complex *_zd, liquid_float_complex *_pd, unsigned int _n,
+                       liquid_float_complex *_zdt, liquid_float_complex *_pdt);
+void iirdes_dzpk_lp2bp(liquid_float_complex *_zd, liquid_float_complex *_pd, unsigned int _n, float _f0,
+                       liquid_float_complex *_zdt, liquid_float_complex *_pdt);
+void iirdes_dzpk2tff(liquid_float_complex *_zd, liquid_float_complex *_pd, unsigned int _n,
+                     liquid_float_complex _kd, float *_b, float *_a);
+/* 1 unless a root of _a (_n coefficients) lies outside the unit circle */
+int iirdes_isstable(float *_b, float *_a, unsigned int _n);
+/* _z sorted into conjugate pairs (within _tol; negative imaginary part first,
+   pairs by increasing real part), the real values after them, increasing */
+void liquid_cplxpair(liquid_float_complex *_z, unsigned int _n, float _tol, liquid_float_complex *_p);
+void liquid_cplxpair_cleanup(liquid_float_complex *_p, unsigned int _n, unsigned int _num_pairs);
+
 /* extension: samples per lane, per workgroup, and tiles per scan block of the
    block-parallel kernels (csrc/k_iirfilt.hip) */
 unsigned int liquid_mi355x_iirfilt_run(void);
 unsigned int liquid_mi355x_iirfilt_tile(void);
 unsigned int liquid_mi355x_iirfilt_scan(void);
+
+/* ------------------------------------------------------------------------ */
+/* iirdecim (liquid.h:2738-2820), iirinterp (liquid.h:2570-2650)             */
+/* ------------------------------------------------------------------------ */
+/* A recursive filter at the full rate, decimated or interpolated by _M >= 2.
+   iirdecim: execute reads _M samples and returns the filter's output for the
+   first of them; execute_block reads _n _M samples and writes _n.  iirinterp:
+   execute feeds _x and _M - 1 zeros and writes _M outputs (no gain
+   compensation); execute_block reads _n samples and writes _n _M.
+   create_default is the Butterworth low-pass of the given order at 0.5 / _M.
+   Extensions: device pointers (_n counted as for execute_block; the input
+   and output ranges must not overlap -- in particular the decimator's
+   execute_block_dev does not support overlapping device ranges, although
+   its host-pointer execute_block allows _y == _x); device_eligible: block
+   calls run on the GPU (the filter is eligible as for iirfilt and _M is at
+   most liquid_mi355x_iirfilt_tile()), else in the host loop. */
+#define LQMI_IIRRATE_API(OBJ, TO, TC, TI, XARG)                                                 \
+    typedef struct OBJ##_s *OBJ;                                                                \
+    OBJ OBJ##_create(unsigned int _M, TC *_b, unsigned int _nb, TC *_a, unsigned int _na);      \
+    OBJ OBJ##_create_default(unsigned int _M, unsigned int _order);                             \
+    OBJ OBJ##_create_prototype(unsigned int _M, liquid_iirdes_filtertype _ftype,                \
+                               liquid_iirdes_bandtype _btype, liquid_iirdes_format _format,     \
+                               unsigned int _order, float _fc, float _f0, float _Ap,            \
+                               float _As);                                                      \
+    void OBJ##_destroy(OBJ _q);                                                                 \
+    void OBJ##_print(OBJ _q);                                                                   \
+    void OBJ##_reset(OBJ _q);                                                                   \
+    void OBJ##_execute(OBJ _q, XARG _x, TO *_y);                                                \
+    void OBJ##_execute_block(OBJ _q, TI *_x, unsigned int _n, TO *_y);                          \
+    float OBJ##_groupdelay(OBJ _q, float _fc);                                                  \
+    void OBJ##_execute_block_dev(OBJ _q, const TI *_dx, unsigned long long _n, TO *_dy);        \
+    int OBJ##_device_eligible(OBJ _q);                                                          \
+    void OBJ##_set_stream(OBJ _q, void *_hip_stream);                                           \
+    void OBJ##_synchronize(OBJ _q);
+
+LQMI_IIRRATE_API(iirdecim_rrrf, float, float, float, float *)
+LQMI_IIRRATE_API(iirdecim_crcf, liquid_float_complex, float, liquid_float_complex, liquid_float_complex *)
+LQMI_IIRRATE_API(iirdecim_cccf, liquid_float_complex, liquid_float_complex, liquid_float_complex,
+                 liquid_float_complex *)
+LQMI_IIRRATE_API(iirinterp_rrrf, float, float, float, float)
+LQMI_IIRRATE_API(iirinterp_crcf, liquid_float_complex, float, liquid_float_complex, liquid_float_complex)
+LQMI_IIRRATE_API(iirinterp_cccf, liquid_float_complex, liquid_float_complex, liquid_float_complex,
+                 liquid_float_complex)
 
 /* ------------------------------------------------------------------------ */
 /* fftfilt (liquid.h:2192-2240): rrrf, crcf, cccf                            */

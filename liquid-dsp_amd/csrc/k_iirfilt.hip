@@ -34,6 +34,21 @@
 // one ds_read_b128 serves together land on 16 different 4-bank slots.  A tile
 // is read whole before any of it is written and nothing outside the tile is
 // touched, so y == x is allowed.
+//
+// The two rate changers (iirdecim.c, iirinterp.c: the full-rate filter with
+// M-1 of every M outputs dropped, or M-1 zeros fed per input) are the same
+// three stages with another tile input or output, chosen by the template
+// parameter MODE of k_iir_tile and k_iir_apply:
+//   DECIM   stage 3 writes only the tile's samples whose full-rate index is a
+//           multiple of M, read from the LDS rows (stride M: bank conflicts
+//           that depend on M) and stored by consecutive lanes to consecutive
+//           outputs.  y is 1/M the size of x, so y == x is not allowed.
+//   INTERP  a tile is TILE output samples; stages 1 and 3 zero the LDS rows
+//           and place the inputs i with base <= i M < base + nvalid at row
+//           position i M - base.  The stuffed stream is never in memory.
+// A long call is cut into pieces of a multiple of M full-rate samples, so a
+// piece starts on a kept sample (an input sample) and the phase within a
+// piece is the full-rate index modulo M.
 #include <hip/hip_runtime.h>
 
 #include "lq_device.h"
@@ -48,6 +63,7 @@ constexpr int TILE = NT * RUN;
 static_assert(TILE == LQK_IIRFILT_TILE, "tile size is part of the interface (tests cut blocks at it)");
 static_assert(NT == LQK_IIRFILT_SCAN, "a scan block takes one vector per lane");
 static_assert(NT == 256 && RUN == 16, "ladder levels below assume 2^4 samples per lane, 2^8 lanes");
+enum { PLAIN = 0, DECIM = 1, INTERP = 2 };
 constexpr int LV_TILE = 0;    // step G_R: lanes of a tile
 constexpr int LV_SCAN = 8;    // step G_R^256: tiles of a chunk
 constexpr int LV_TOP = 16;    // step G_R^65536: chunks of a piece
@@ -235,6 +251,38 @@ template <class S> struct tile_io {
         }
     }
 
+    // INTERP: the tile's first nvalid full-rate samples, base the full-rate index
+    // of the first, of the input x stuffed with M - 1 zeros per sample
+    static DI void load_stuffed(const S *x, long long base, int nvalid, int M, float *lds)
+    {
+        const int t = threadIdx.x;
+#pragma unroll
+        for (int it = 0; it < IT; it++) {
+            const int d = 4 * (it * NT + t);
+            *reinterpret_cast<float4 *>(lds + d + (d / RW) * 4) = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+        __syncthreads();
+        const long long i0 = (base + M - 1) / M, i1 = (base + nvalid - 1) / M;   // inputs i0 .. i1
+        const int cnt = i1 >= i0 ? (int)(i1 - i0 + 1) : 0, pos0 = (int)(i0 * M - base);
+        for (int k = t; k < cnt; k += NT) {
+            const int d = (pos0 + k * M) * W;
+            unpack(x[i0 + k], lds + d + (d / RW) * 4);
+        }
+    }
+
+    // DECIM: the tile's samples at full-rate indices that are multiples of M
+    // (base the index of the tile's first) to y[index / M]
+    static DI void store_kept(S *y, long long base, int nvalid, int M, const float *lds)
+    {
+        const int j0 = (int)((M - base % M) % M);
+        const int cnt = j0 < nvalid ? (nvalid - j0 - 1) / M + 1 : 0;
+        S *y0 = y + (base + j0) / M;
+        for (int k = threadIdx.x; k < cnt; k += NT) {
+            const int d = (j0 + k * M) * W;
+            y0[k] = pack(lds + d + (d / RW) * 4);
+        }
+    }
+
     static DI void get_run(const float *lds, S (&x)[RUN])
     {
         const float4 *p = reinterpret_cast<const float4 *>(lds + threadIdx.x * ROW);
@@ -270,12 +318,13 @@ template <class S> struct tile_io {
     }
 };
 
-// stage 1: z[tile] for the full tiles blockIdx.x
-template <int KIND, int MS>
+// stage 1: z[tile] for the full tiles blockIdx.x (INTERP: x is the input
+// before stuffing by M)
+template <int KIND, int MS, int MODE>
 __global__ __launch_bounds__(NT) void k_iir_tile(const typename iir_t<KIND>::K *__restrict__ coef, int nsec,
                                                  const typename iir_t<KIND>::K *__restrict__ lad,
                                                  const typename iir_t<KIND>::S *x, int vec,
-                                                 typename iir_t<KIND>::S *__restrict__ z)
+                                                 typename iir_t<KIND>::S *__restrict__ z, int M)
 {
     using S = typename iir_t<KIND>::S;
     using IO = tile_io<S>;
@@ -283,7 +332,8 @@ __global__ __launch_bounds__(NT) void k_iir_tile(const typename iir_t<KIND>::K *
     __shared__ __attribute__((aligned(16))) float lds[IO::LDS];
     __shared__ S wt[NW * PM];
     const int P = 2 * nsec;
-    IO::load(x + (size_t)blockIdx.x * TILE, TILE, vec != 0, lds);
+    if constexpr (MODE == INTERP) IO::load_stuffed(x, (long long)blockIdx.x * TILE, TILE, M, lds);
+    else IO::load(x + (size_t)blockIdx.x * TILE, TILE, vec != 0, lds);
     __syncthreads();
     S xr[RUN], st[PM], carry[PM], total[PM];
     IO::get_run(lds, xr);
@@ -300,13 +350,15 @@ __global__ __launch_bounds__(NT) void k_iir_tile(const typename iir_t<KIND>::K *
 // stage 3: tile blockIdx.x of the n samples from start[tile] to y; the last
 // tile leaves the state after sample n-1 in state_out (start may be state_out
 // when there is one tile: every lane has read it before the barrier in
-// block_scan, the writer stores after it)
-template <int KIND, int MS>
+// block_scan, the writer stores after it).  n counts full-rate samples: DECIM
+// writes the n / M kept ones, INTERP reads n / M inputs.
+template <int KIND, int MS, int MODE>
 __global__ __launch_bounds__(NT) void k_iir_apply(const typename iir_t<KIND>::K *__restrict__ coef, int nsec,
                                                   const typename iir_t<KIND>::K *__restrict__ lad,
                                                   const typename iir_t<KIND>::S *x, long long n, int vec,
                                                   const typename iir_t<KIND>::S *start, int start_stride,
-                                                  typename iir_t<KIND>::S *y, typename iir_t<KIND>::S *state_out)
+                                                  typename iir_t<KIND>::S *y, typename iir_t<KIND>::S *state_out,
+                                                  int M)
 {
     using S = typename iir_t<KIND>::S;
     using IO = tile_io<S>;
@@ -316,7 +368,8 @@ __global__ __launch_bounds__(NT) void k_iir_apply(const typename iir_t<KIND>::K 
     const int P = 2 * nsec, t = threadIdx.x;
     const long long base = (long long)blockIdx.x * TILE;
     const int nvalid = n - base < TILE ? (int)(n - base) : TILE;
-    IO::load(x + base, nvalid, vec != 0, lds);
+    if constexpr (MODE == INTERP) IO::load_stuffed(x, base, nvalid, M, lds);
+    else IO::load(x + base, nvalid, vec != 0, lds);
     S carry[PM];
 #pragma unroll
     for (int r = 0; r < PM; r++) carry[r] = r < P ? start[(size_t)blockIdx.x * start_stride + r] : izero<S>();
@@ -338,7 +391,8 @@ __global__ __launch_bounds__(NT) void k_iir_apply(const typename iir_t<KIND>::K 
         }
     }
     __syncthreads();
-    IO::store(y + base, nvalid, vec != 0, lds);
+    if constexpr (MODE == DECIM) IO::store_kept(y, base, nvalid, M, lds);
+    else IO::store(y + base, nvalid, vec != 0, lds);
 }
 
 // stage 2: block b scans the vectors z[256 b + lane] (zero from nz on) from
@@ -377,9 +431,11 @@ __global__ __launch_bounds__(NT) void k_iir_scan(const typename iir_t<KIND>::K *
 
 constexpr unsigned long long PIECE = (unsigned long long)TILE * NT * NT;   // samples per three-stage pass
 
-template <int KIND, int MS>
+// n full-rate samples; vec: the 16-byte global accesses of the mode (DECIM
+// loads, INTERP stores, PLAIN both) are aligned
+template <int KIND, int MS, int MODE>
 void run_piece(unsigned int nsec, const void *coef_, const void *lad_, void *state_, const void *x_,
-               unsigned long long n, void *y_, void *work, hipStream_t st)
+               unsigned long long n, int M, void *y_, void *work, hipStream_t st)
 {
     using S = typename iir_t<KIND>::S;
     using K = typename iir_t<KIND>::K;
@@ -387,18 +443,18 @@ void run_piece(unsigned int nsec, const void *coef_, const void *lad_, void *sta
     const K *coef = (const K *)coef_, *lad = (const K *)lad_;
     S *state = (S *)state_, *y = (S *)y_;
     const S *x = (const S *)x_;
-    const int vec = (((uintptr_t)x_ | (uintptr_t)y_) & 15) == 0;
+    const int vec = (((MODE == INTERP ? 0 : (uintptr_t)x_) | (MODE == DECIM ? 0 : (uintptr_t)y_)) & 15) == 0;
     const long long ntiles = (long long)((n + TILE - 1) / TILE);
     if (ntiles == 1) {
-        hipLaunchKernelGGL((k_iir_apply<KIND, MS>), dim3(1), dim3(NT), 0, st, coef, (int)nsec, lad, x, (long long)n,
-                           vec, (const S *)state, 0, y, state);
+        hipLaunchKernelGGL((k_iir_apply<KIND, MS, MODE>), dim3(1), dim3(NT), 0, st, coef, (int)nsec, lad, x,
+                           (long long)n, vec, (const S *)state, 0, y, state, M);
         LQ_CHECK_LAUNCH();
         return;
     }
     const long long nch = (ntiles + NT - 1) / NT;
     S *z = (S *)work, *start = z + ntiles * PM, *ctot = start + ntiles * PM, *cstart = ctot + nch * PM;
-    hipLaunchKernelGGL((k_iir_tile<KIND, MS>), dim3((unsigned)(ntiles - 1)), dim3(NT), 0, st, coef, (int)nsec, lad, x,
-                       vec, z);
+    hipLaunchKernelGGL((k_iir_tile<KIND, MS, MODE == INTERP ? INTERP : PLAIN>), dim3((unsigned)(ntiles - 1)), dim3(NT),
+                       0, st, coef, (int)nsec, lad, x, vec, z, M);
     LQ_CHECK_LAUNCH();
     if (nch == 1) {
         hipLaunchKernelGGL((k_iir_scan<KIND, MS>), dim3(1), dim3(NT), 0, st, lad + LV_SCAN * PM * PM, (int)nsec,
@@ -415,9 +471,32 @@ void run_piece(unsigned int nsec, const void *coef_, const void *lad_, void *sta
                            (int)nsec, (const S *)z, ntiles - 1, (const S *)cstart, start, ntiles, (S *)nullptr);
         LQ_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL((k_iir_apply<KIND, MS>), dim3((unsigned)ntiles), dim3(NT), 0, st, coef, (int)nsec, lad, x,
-                       (long long)n, vec, (const S *)start, PM, y, state);
+    hipLaunchKernelGGL((k_iir_apply<KIND, MS, MODE>), dim3((unsigned)ntiles), dim3(NT), 0, st, coef, (int)nsec, lad,
+                       x, (long long)n, vec, (const S *)start, PM, y, state, M);
     LQ_CHECK_LAUNCH();
+}
+
+// n full-rate samples in pieces of at most PIECE, a multiple of M each
+template <int MODE>
+void run_all(int kind, unsigned int nsec, const void *coef, const void *ladder, void *state, const void *x,
+             unsigned long long n, unsigned int M, void *y, void *work, void *stream, const char *who)
+{
+    hipStream_t st = (hipStream_t)stream;
+    const size_t esz = kind == 0 ? 4 : 8;
+    if (M == 0 || M > PIECE) lq_check(hipErrorInvalidValue, who, __FILE__, __LINE__);
+    const unsigned long long piece = PIECE / M * M;
+    for (unsigned long long i = 0; i < n; i += piece) {
+        const unsigned long long m = n - i < piece ? n - i : piece;
+        const void *xi = (const char *)x + (MODE == INTERP ? i / M : i) * esz;
+        void *yi = (char *)y + (MODE == DECIM ? i / M : i) * esz;
+        const bool ok = lq_switch<1, 2, 4, 8>((int)lqk_iirfilt_maxsec(nsec), [&](auto ms) {
+            constexpr int MS = decltype(ms)::value;
+            if (kind == 0) run_piece<0, MS, MODE>(nsec, coef, ladder, state, xi, m, (int)M, yi, work, st);
+            else if (kind == 1) run_piece<1, MS, MODE>(nsec, coef, ladder, state, xi, m, (int)M, yi, work, st);
+            else run_piece<2, MS, MODE>(nsec, coef, ladder, state, xi, m, (int)M, yi, work, st);
+        });
+        if (!ok) lq_check(hipErrorInvalidValue, who, __FILE__, __LINE__);
+    }
 }
 
 } // namespace
@@ -440,17 +519,26 @@ extern "C" size_t lqk_iirfilt_work_bytes(int kind, unsigned int nsec, unsigned l
 extern "C" void lqk_iirfilt(int kind, unsigned int nsec, const void *coef, const void *ladder, void *state,
                             const void *x, unsigned long long n, void *y, void *work, void *stream)
 {
-    hipStream_t st = (hipStream_t)stream;
-    const size_t esz = kind == 0 ? 4 : 8;
-    for (unsigned long long i = 0; i < n; i += PIECE) {
-        const unsigned long long m = n - i < PIECE ? n - i : PIECE;
-        const void *xi = (const char *)x + i * esz;
-        void *yi = (char *)y + i * esz;
-        const bool ok = lq_switch<1, 2, 4, 8>((int)lqk_iirfilt_maxsec(nsec), [&](auto ms) {
-            if (kind == 0) run_piece<0, decltype(ms)::value>(nsec, coef, ladder, state, xi, m, yi, work, st);
-            else if (kind == 1) run_piece<1, decltype(ms)::value>(nsec, coef, ladder, state, xi, m, yi, work, st);
-            else run_piece<2, decltype(ms)::value>(nsec, coef, ladder, state, xi, m, yi, work, st);
-        });
-        if (!ok) lq_check(hipErrorInvalidValue, "lqk_iirfilt: more than 8 sections", __FILE__, __LINE__);
-    }
+    run_all<PLAIN>(kind, nsec, coef, ladder, state, x, n, 1, y, work, stream, "lqk_iirfilt: more than 8 sections");
+}
+
+extern "C" void lqk_iirfilt_decim(int kind, unsigned int nsec, const void *coef, const void *ladder, void *state,
+                                  const void *x, unsigned long long n_in, unsigned int M, void *y, void *work,
+                                  void *stream)
+{
+    if (M > LQK_IIRFILT_TILE || n_in % (M ? M : 1) != 0)
+        lq_check(hipErrorInvalidValue, "lqk_iirfilt_decim: M above the tile size, or n_in not a multiple of M", __FILE__,
+                 __LINE__);
+    run_all<DECIM>(kind, nsec, coef, ladder, state, x, n_in, M, y, work, stream,
+                   "lqk_iirfilt_decim: more than 8 sections, or M = 0");
+}
+
+extern "C" void lqk_iirfilt_interp(int kind, unsigned int nsec, const void *coef, const void *ladder, void *state,
+                                   const void *x, unsigned long long n_in, unsigned int M, void *y, void *work,
+                                   void *stream)
+{
+    if (M > LQK_IIRFILT_TILE)
+        lq_check(hipErrorInvalidValue, "lqk_iirfilt_interp: M above the tile size", __FILE__, __LINE__);
+    run_all<INTERP>(kind, nsec, coef, ladder, state, x, n_in * M, M, y, work, stream,
+                    "lqk_iirfilt_interp: more than 8 sections, or M = 0");
 }

@@ -360,6 +360,19 @@ unsigned int lqk_iirfilt_maxsec(unsigned int nsec);
 size_t lqk_iirfilt_work_bytes(int kind, unsigned int nsec, unsigned long long n);
 void lqk_iirfilt(int kind, unsigned int nsec, const void *coef, const void *ladder, void *state, const void *x,
                  unsigned long long n, void *y, void *work, void *stream);
+/* The same filter as a rate changer by M, 1 <= M <= LQK_IIRFILT_TILE, with the
+ * same coef / ladder / state / work contracts; work is sized by the full-rate
+ * sample count (n_in for the decimator, n_in M for the interpolator).
+ *   decim   x: n_in samples, n_in a multiple of M; y: n_in / M samples, the
+ *           filter's outputs at the indices that are multiples of M.  x and y
+ *           must not overlap.
+ *   interp  x: n_in samples; y: n_in M samples, the filter's outputs for x[i]
+ *           followed by M - 1 zeros each.  x and y must not overlap.
+ * The state is left as after the last full-rate sample. */
+void lqk_iirfilt_decim(int kind, unsigned int nsec, const void *coef, const void *ladder, void *state, const void *x,
+                       unsigned long long n_in, unsigned int M, void *y, void *work, void *stream);
+void lqk_iirfilt_interp(int kind, unsigned int nsec, const void *coef, const void *ladder, void *state, const void *x,
+                        unsigned long long n_in, unsigned int M, void *y, void *work, void *stream);
 
 #ifdef __cplusplus
 }

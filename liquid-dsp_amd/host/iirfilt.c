@@ -1,9 +1,11 @@
 /*
  * iirfilt.c -- iirfilt_{rrrf,crcf,cccf}: recursive (infinite impulse
- * response) filters, and the design helpers their constructors need.
+ * response) filters, the engine behind them (lq_iir in lq_host.h, which
+ * iirdecim.c runs as a decimator or an interpolator), and the PLL and
+ * group-delay helpers.  The filter designs are in iirdes.c.
  *
  * include/liquid.h:2247-2378, src/filter/src/iirfilt.c, iirfiltsos.c,
- * iirdes.c:60-184,320-406, iirdes.pll.c, group_delay.c:64-117.
+ * iirdes.pll.c, group_delay.c:64-117.
  *   NORM form (create): coefficients divided by a[0]; direct form II over
  *     n = max(nb, na) states v[0..n-1]:
  *       v[i] <- v[i-1];  v[0] = x - sum_{i>=1} a[i] v[i];  y = sum b[i] v[i]
@@ -27,8 +29,18 @@
  * the small-call rule (lq_small.c): the host loop unless LQ_SMALL_CALLS=gpu.
  * The host loop is the reference's statement order in float32.
  *
- * create_prototype and create_lowpass (the analog prototype designs) are not
- * provided and not declared.
+ * iirfilt_*_create_prototype and _create_lowpass stay undeclared and are not
+ * exported (tests/test_iirfilt_model.py holds the library to that): a caller
+ * designs with liquid_iirdes (iirdes.c) and passes the result to create_sos
+ * or create.  The engine's own lq_iir_create_prototype does exactly that for
+ * iirdecim and iirinterp.
+ *
+ * Rate changing (lq_iir_run_rate; iirdecim.c:121-145, iirinterp.c:120-141):
+ * the same filter at the full rate with M - 1 of every M outputs dropped
+ * (the first of each group of M is kept), or with M - 1 zeros fed after each
+ * input.  On the device neither the dropped outputs nor the zeros are ever in
+ * memory (lqk_iirfilt_decim, lqk_iirfilt_interp); M above LQK_IIRFILT_TILE,
+ * like an object that is not eligible, runs the host loop with the stride.
  */
 #include <complex.h>
 #include <math.h>
@@ -37,7 +49,7 @@
 
 static const char *const kind_name[3] = {"rrrf", "crcf", "cccf"};
 
-typedef struct {
+struct lq_iir_s {
     int kind, sos;
     unsigned int nb, na, n, nsos;
     int cw, sw;               /* floats per coefficient / per sample */
@@ -49,7 +61,7 @@ typedef struct {
     lq_mirror sm;             /* the state (host side; device side d_state) */
     lq_ctx ctx;
     lq_devbuf xbuf, ybuf, work;
-} lq_iir;
+};
 
 /* ------------------------------------------------------------------ float32 arithmetic of one kind */
 #define LQ_INL static inline __attribute__((always_inline))
@@ -138,6 +150,47 @@ static void host_loop(lq_iir *q, const void *x, unsigned long long n, void *y)
         host_loop_k(LQ_CRCF, q, s, (const float *)x, n, (float *)y);
     else
         host_loop_k(LQ_CCCF, q, s, (const float *)x, n, (float *)y);
+    q->sm.dev_valid = 0;
+}
+
+/* nf full-rate samples: mode 1 reads them all and keeps the outputs at the
+ * multiples of M (y may be x: output i / M is written after input i is read),
+ * mode 2 reads x[i / M] at the multiples of M and zero elsewhere */
+LQ_INL void host_rate_k(int kind, const lq_iir *q, float *s, int mode, unsigned int M, const float *x,
+                        unsigned long long nf, float *y)
+{
+    const int sw = kind == LQ_RRRF ? 1 : 2;
+    const float zero[2] = {0.0f, 0.0f};
+    float t[2];
+    unsigned int ph = 0;   /* i mod M */
+    for (unsigned long long i = 0, k = 0; i < nf; i++) {
+        const float *in = mode == 1 ? x + sw * i : (ph == 0 ? x + sw * k : zero);
+        if (q->sos)
+            sos_step(kind, q, s, in, t);
+        else
+            norm_step(kind, q, s, in, t);
+        float *out = mode == 1 ? y + sw * k : y + sw * i;
+        if (mode == 2 || ph == 0)
+            for (int c = 0; c < sw; c++) out[c] = t[c];
+        if (ph == 0 && mode == 1) k++;
+        if (++ph == M) {
+            ph = 0;
+            if (mode == 2) k++;
+        }
+    }
+}
+
+static void host_rate(lq_iir *q, int mode, unsigned int M, const void *x, unsigned long long nf, void *y)
+{
+    if (nf == 0) return;
+    lq_mirror_need_host(&q->sm, q->d_state, q->ctx.stream);
+    float *s = (float *)lq_mirror_ptr(&q->sm);
+    if (q->kind == LQ_RRRF)
+        host_rate_k(LQ_RRRF, q, s, mode, M, (const float *)x, nf, (float *)y);
+    else if (q->kind == LQ_CRCF)
+        host_rate_k(LQ_CRCF, q, s, mode, M, (const float *)x, nf, (float *)y);
+    else
+        host_rate_k(LQ_CCCF, q, s, mode, M, (const float *)x, nf, (float *)y);
     q->sm.dev_valid = 0;
 }
 
@@ -330,8 +383,8 @@ static lq_iir *iir_create_sos(int kind, const void *_B, const void *_A, unsigned
 /* real design coefficients as the kind's coefficient type */
 static lq_iir *iir_from_real(int kind, int sos, const float *b, unsigned int nb, const float *a, unsigned int na)
 {
-    float cb[2 * 12], ca[2 * 12];
     const int cw = kind == LQ_CCCF ? 2 : 1;
+    float *cb = (float *)lq_xmalloc((size_t)(nb + na) * cw * sizeof(float)), *ca = cb + (size_t)nb * cw;
     for (unsigned int i = 0; i < nb; i++) {
         cb[cw * i] = b[i];
         if (cw == 2) cb[2 * i + 1] = 0.0f;
@@ -340,7 +393,26 @@ static lq_iir *iir_from_real(int kind, int sos, const float *b, unsigned int nb,
         ca[cw * i] = a[i];
         if (cw == 2) ca[2 * i + 1] = 0.0f;
     }
-    return sos ? iir_create_sos(kind, cb, ca, nb / 3) : iir_create(kind, cb, nb, ca, na);
+    lq_iir *q = sos ? iir_create_sos(kind, cb, ca, nb / 3) : iir_create(kind, cb, nb, ca, na);
+    free(cb);
+    return q;
+}
+
+/* iirfilt.c:196-241: the design's length follows its order, doubled by the
+ * band-pass and band-stop transforms */
+static lq_iir *iir_create_prototype(int kind, liquid_iirdes_filtertype ftype, liquid_iirdes_bandtype btype,
+                                    liquid_iirdes_format format, unsigned int order, float fc, float f0, float Ap,
+                                    float As)
+{
+    unsigned int N = order;
+    if (btype == LIQUID_IIRDES_BANDPASS || btype == LIQUID_IIRDES_BANDSTOP) N *= 2;
+    const unsigned int r = N % 2, L = (N - r) / 2;
+    const unsigned int h_len = format == LIQUID_IIRDES_SOS ? 3 * (L + r) : N + 1;
+    float *B = (float *)lq_xmalloc(2 * (size_t)h_len * sizeof(float)), *A = B + h_len;
+    liquid_iirdes(ftype, btype, format, order, fc, f0, Ap, As, B, A);
+    lq_iir *q = iir_from_real(kind, format == LIQUID_IIRDES_SOS, B, h_len, A, h_len);
+    free(B);
+    return q;
 }
 
 /* [Pintelon:1990] R. Pintelon and J. Schoukens, "Real-time integration and
@@ -511,6 +583,52 @@ static void iir_execute(lq_iir *q, const void *x, void *y)
         iir_run(q, x, 1, y);
 }
 
+/* ------------------------------------------------------------------ as a rate changer */
+static int rate_dev_ok(const lq_iir *q, unsigned int M) { return q->dev_ok && M <= LQK_IIRFILT_TILE; }
+
+/* n calls' worth: mode 1 n M samples in, n out; mode 2 n in, n M out */
+static void iir_rate_dev(lq_iir *q, int mode, unsigned int M, const void *dx, unsigned long long n, void *dy)
+{
+    if (n == 0) return;
+    const unsigned long long nf = n * M, nin = mode == 1 ? nf : n, nout = mode == 1 ? n : nf;
+    if (!rate_dev_ok(q, M)) {   /* device pointers, host loop: copy, run, copy back */
+        const size_t esz = q->sw * sizeof(float);
+        void *hx = lq_xmalloc((size_t)nin * esz), *hy = lq_xmalloc((size_t)nout * esz);
+        lqrt_d2h(hx, dx, (size_t)nin * esz, q->ctx.stream);
+        lqrt_sync(q->ctx.stream);
+        host_rate(q, mode, M, hx, nf, hy);
+        lqrt_h2d(dy, hy, (size_t)nout * esz, q->ctx.stream);
+        lqrt_sync(q->ctx.stream);
+        free(hx);
+        free(hy);
+        return;
+    }
+    lq_mirror_need_dev(&q->sm, q->d_state, q->ctx.stream);
+    q->sm.host_valid = 0;
+    const size_t wb = lqk_iirfilt_work_bytes(q->kind, q->nsec, nf);
+    void *work = wb ? lq_devbuf_get(&q->work, wb) : NULL;
+    if (mode == 1)
+        lqk_iirfilt_decim(q->kind, q->nsec, q->d_coef, q->d_lad, q->d_state, dx, nf, M, dy, work, q->ctx.stream);
+    else
+        lqk_iirfilt_interp(q->kind, q->nsec, q->d_coef, q->d_lad, q->d_state, dx, n, M, dy, work, q->ctx.stream);
+}
+
+static void iir_rate(lq_iir *q, int mode, unsigned int M, const void *x, unsigned long long n, void *y, int small)
+{
+    if (n == 0) return;
+    const unsigned long long nf = n * M;
+    if (!rate_dev_ok(q, M) || (small && lq_small_host())) {
+        host_rate(q, mode, M, x, nf, y);
+        return;
+    }
+    const size_t esz = q->sw * sizeof(float);
+    const size_t bin = (size_t)(mode == 1 ? nf : n) * esz, bout = (size_t)(mode == 1 ? n : nf) * esz;
+    const void *dx = lq_call_in(&q->ctx, &q->xbuf, x, bin);   /* staged: y may be x */
+    void *dy = lq_devbuf_get(&q->ybuf, bout);
+    iir_rate_dev(q, mode, M, dx, n, dy);
+    lq_call_out(&q->ctx, y, dy, bout);
+}
+
 static void iir_freqresponse(const lq_iir *q, float fc, liquid_float_complex *H)   /* iirfilt.c:587-628 */
 {
     const int cw = q->cw;
@@ -591,94 +709,6 @@ void iirdes_pll_active_PI(float _w, float _zeta, float _K, float *_b, float *_a)
     _a[2] = t1 / 2.0f;
 }
 
-/* iirdes.c:60-184 (liquid_cplxpair and its clean-up): p = the n values of z
- * with the conjugate pairs first (negative imaginary part first, pairs by
- * increasing real part, made exact conjugates) and the real values after
- * them in increasing order */
-static void cplxpair(const float complex *z, unsigned int n, float tol, float complex *p)
-{
-    unsigned char *used = (unsigned char *)lq_xmalloc(n ? n : 1);
-    memset(used, 0, n ? n : 1);
-    unsigned int k = 0, npairs = 0;
-    for (unsigned int i = 0; i < n; i++) {
-        if (used[i] || fabsf(cimagf(z[i])) < tol) continue;
-        for (unsigned int j = 0; j < n; j++) {
-            if (j == i || used[j] || fabsf(cimagf(z[j])) < tol) continue;
-            if (fabsf(cimagf(z[i]) + cimagf(z[j])) < tol && fabsf(crealf(z[i]) - crealf(z[j])) < tol) {
-                p[k++] = z[i];
-                p[k++] = z[j];
-                used[i] = used[j] = 1;
-                npairs++;
-                break;
-            }
-        }
-    }
-    for (unsigned int i = 0; i < n; i++) {
-        if (used[i]) continue;
-        if (cimagf(z[i]) > tol) {
-            fprintf(stderr, "warning, liquid_cplxpair(), complex numbers cannot be paired\n");
-        } else {
-            p[k++] = z[i];
-            used[i] = 1;
-        }
-    }
-    free(used);
-    for (unsigned int i = 0; i < npairs; i++) {
-        if (!(cimagf(p[2 * i]) < 0)) p[2 * i] = conjf(p[2 * i]);
-        p[2 * i + 1] = conjf(p[2 * i]);
-    }
-    for (unsigned int i = 0; i < npairs; i++)          /* bubble sort, pairs by real part */
-        for (unsigned int j = npairs - 1; j > i; j--)
-            if (crealf(p[2 * (j - 1)]) > crealf(p[2 * j]))
-                for (int c = 0; c < 2; c++) {
-                    const float complex t = p[2 * (j - 1) + c];
-                    p[2 * (j - 1) + c] = p[2 * j + c];
-                    p[2 * j + c] = t;
-                }
-    for (unsigned int i = 2 * npairs; i < n; i++)      /* the real values */
-        for (unsigned int j = n - 1; j > i; j--)
-            if (crealf(p[j - 1]) > crealf(p[j])) {
-                const float complex t = p[j - 1];
-                p[j - 1] = p[j];
-                p[j] = t;
-            }
-}
-
-/* iirdes.c:320-406: zeros, poles and gain to L + r second-order sections
- * (n = 2L + r), the gain spread evenly over the numerators */
-void iirdes_dzpk2sosf(liquid_float_complex *_zd, liquid_float_complex *_pd, unsigned int _n,
-                      liquid_float_complex _kd, float *_B, float *_A)
-{
-    float complex *zp = (float complex *)lq_xmalloc((_n ? _n : 1) * sizeof(float complex));
-    float complex *pp = (float complex *)lq_xmalloc((_n ? _n : 1) * sizeof(float complex));
-    cplxpair((const float complex *)_zd, _n, 1e-6f, zp);
-    cplxpair((const float complex *)_pd, _n, 1e-6f, pp);
-    const unsigned int r = _n % 2, L = (_n - r) / 2;
-    for (unsigned int i = 0; i < L; i++) {
-        const float complex p0 = -pp[2 * i], p1 = -pp[2 * i + 1], z0 = -zp[2 * i], z1 = -zp[2 * i + 1];
-        _A[3 * i] = 1.0f;
-        _A[3 * i + 1] = crealf(p0 + p1);
-        _A[3 * i + 2] = crealf(p0 * p1);
-        _B[3 * i] = 1.0f;
-        _B[3 * i + 1] = crealf(z0 + z1);
-        _B[3 * i + 2] = crealf(z0 * z1);
-    }
-    if (r) {
-        _A[3 * L] = 1.0f;
-        _A[3 * L + 1] = crealf(-pp[_n - 1]);
-        _A[3 * L + 2] = 0.0f;
-        _B[3 * L] = 1.0f;
-        _B[3 * L + 1] = crealf(-zp[_n - 1]);
-        _B[3 * L + 2] = 0.0f;
-    }
-    float complex kd;
-    memcpy(&kd, &_kd, sizeof(kd));
-    const float k = powf(crealf(kd), 1.0f / (float)(L + r));
-    for (unsigned int i = 0; i < 3 * (L + r); i++) _B[i] *= k;
-    free(zp);
-    free(pp);
-}
-
 /* group_delay.c:64-117 */
 float iir_group_delay(float *_b, unsigned int _nb, float *_a, unsigned int _na, float _fc)
 {
@@ -701,6 +731,32 @@ float iir_group_delay(float *_b, unsigned int _nb, float *_a, unsigned int _na, 
     return crealf(t0 / t1) - (_na - 1);
 }
 
+/* the engine as iirdecim.c sees it (lq_host.h) */
+lq_iir *lq_iir_create(int kind, const void *b, unsigned int nb, const void *a, unsigned int na)
+{
+    return iir_create(kind, b, nb, a, na);
+}
+lq_iir *lq_iir_create_prototype(int kind, liquid_iirdes_filtertype ftype, liquid_iirdes_bandtype btype,
+                                liquid_iirdes_format format, unsigned int order, float fc, float f0, float Ap,
+                                float As)
+{
+    return iir_create_prototype(kind, ftype, btype, format, order, fc, f0, Ap, As);
+}
+void lq_iir_destroy(lq_iir *q) { iir_destroy(q); }
+void lq_iir_print(lq_iir *q) { iir_print(q); }
+void lq_iir_reset(lq_iir *q) { iir_reset(q); }
+float lq_iir_groupdelay(lq_iir *q, float fc) { return iir_groupdelay(q, fc); }
+int lq_iir_rate_eligible(lq_iir *q, unsigned int M) { return rate_dev_ok(q, M); }
+lq_ctx *lq_iir_ctx(lq_iir *q) { return &q->ctx; }
+void lq_iir_run_rate(lq_iir *q, int mode, unsigned int M, const void *x, unsigned long long n, void *y, int small)
+{
+    iir_rate(q, mode, M, x, n, y, small);
+}
+void lq_iir_run_rate_dev(lq_iir *q, int mode, unsigned int M, const void *dx, unsigned long long n, void *dy)
+{
+    iir_rate_dev(q, mode, M, dx, n, dy);
+}
+
 /* block geometry of the device path (tests cut streams at these) */
 unsigned int liquid_mi355x_iirfilt_run(void) { return LQK_IIRFILT_RUN; }
 unsigned int liquid_mi355x_iirfilt_tile(void) { return LQK_IIRFILT_TILE; }
@@ -709,7 +765,7 @@ unsigned int liquid_mi355x_iirfilt_scan(void) { return LQK_IIRFILT_SCAN; }
 /* ------------------------------------------------------------------ typed front ends */
 #define LQ_IIRFILT_DEFINE(IIRFILT, KIND, TO, TC, TI)                                                          \
     struct IIRFILT##_s {                                                                                      \
-        lq_iir e;                                                                                             \
+        struct lq_iir_s e;                                                                                    \
     };                                                                                                        \
     IIRFILT IIRFILT##_create(TC *_b, unsigned int _nb, TC *_a, unsigned int _na)                              \
     {                                                                                                         \

@@ -186,6 +186,25 @@ void lq_firfilt_execute_block_dev(lq_firfilt *q, const void *dx, unsigned long l
 unsigned int lq_firfilt_get_length(lq_firfilt *q);
 lq_ctx *lq_firfilt_ctx(lq_firfilt *q);
 
+/* recursive filter engine (host/iirfilt.c) as the rate changers use it
+ * (host/iirdecim.c).  mode 1: decimate by M (n M samples in, n out, the first
+ * output of each group of M); mode 2: interpolate by M (n in, n M out, M - 1
+ * zeros fed after each input).  small: the call is a single execute, which
+ * follows the small-call rule.  rate_eligible: block calls run on the GPU. */
+typedef struct lq_iir_s lq_iir;
+lq_iir *lq_iir_create(int kind, const void *b, unsigned int nb, const void *a, unsigned int na);
+lq_iir *lq_iir_create_prototype(int kind, liquid_iirdes_filtertype ftype, liquid_iirdes_bandtype btype,
+                                liquid_iirdes_format format, unsigned int order, float fc, float f0, float Ap,
+                                float As);
+void lq_iir_destroy(lq_iir *q);
+void lq_iir_print(lq_iir *q);
+void lq_iir_reset(lq_iir *q);
+float lq_iir_groupdelay(lq_iir *q, float fc);
+int lq_iir_rate_eligible(lq_iir *q, unsigned int M);
+lq_ctx *lq_iir_ctx(lq_iir *q);
+void lq_iir_run_rate(lq_iir *q, int mode, unsigned int M, const void *x, unsigned long long n, void *y, int small);
+void lq_iir_run_rate_dev(lq_iir *q, int mode, unsigned int M, const void *dx, unsigned long long n, void *dy);
+
 /* arbitrary-rate resampler engine (host/resamp.c), used by msresamp */
 typedef struct lq_rs_s lq_rs;
 lq_rs *lq_rs_create(int kind, float rate, unsigned int m, float fc, float As, unsigned int npfb);

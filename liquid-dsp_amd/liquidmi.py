@@ -290,8 +290,38 @@ def _declare(L):
             "iirfilt_%s_set_stream" % t: (None, [vp, vp]),
             "iirfilt_%s_synchronize" % t: (None, [vp]),
         })
+        for obj, xarg in (("iirdecim", vp), ("iirinterp", ti)):
+            sig.update({
+                "%s_%s_create" % (obj, t): (vp, [u, vp, u, vp, u]),
+                "%s_%s_create_default" % (obj, t): (vp, [u, u]),
+                "%s_%s_create_prototype" % (obj, t): (vp, [u, i, i, i, u, f, f, f, f]),
+                "%s_%s_destroy" % (obj, t): (None, [vp]),
+                "%s_%s_print" % (obj, t): (None, [vp]),
+                "%s_%s_reset" % (obj, t): (None, [vp]),
+                "%s_%s_execute" % (obj, t): (None, [vp, xarg, vp]),
+                "%s_%s_execute_block" % (obj, t): (None, [vp, vp, u, vp]),
+                "%s_%s_execute_block_dev" % (obj, t): (None, [vp, vp, ull, vp]),
+                "%s_%s_groupdelay" % (obj, t): (f, [vp, f]),
+                "%s_%s_device_eligible" % (obj, t): (i, [vp]),
+                "%s_%s_set_stream" % (obj, t): (None, [vp, vp]),
+                "%s_%s_synchronize" % (obj, t): (None, [vp]),
+            })
     sig.update({
         "iir_group_delay": (f, [vp, u, vp, u, f]),
+        "liquid_iirdes": (None, [i, i, i, u, f, f, f, f, vp, vp]),
+        "butter_azpkf": (None, [u, vp, vp, vp]),
+        "cheby1_azpkf": (None, [u, f, vp, vp, vp]),
+        "cheby2_azpkf": (None, [u, f, vp, vp, vp]),
+        "ellip_azpkf": (None, [u, f, f, vp, vp, vp]),
+        "bessel_azpkf": (None, [u, vp, vp, vp]),
+        "iirdes_freqprewarp": (f, [i, f, f]),
+        "bilinear_zpkf": (None, [vp, u, vp, u, cfloat, f, vp, vp, vp]),
+        "iirdes_dzpk_lp2hp": (None, [vp, vp, u, vp, vp]),
+        "iirdes_dzpk_lp2bp": (None, [vp, vp, u, f, vp, vp]),
+        "iirdes_dzpk2tff": (None, [vp, vp, u, cfloat, vp, vp]),
+        "iirdes_isstable": (i, [vp, vp, u]),
+        "liquid_cplxpair": (None, [vp, u, f, vp]),
+        "liquid_cplxpair_cleanup": (None, [vp, u, u]),
         "iirdes_dzpk2sosf": (None, [vp, vp, u, cfloat, vp, vp]),
         "iirdes_pll_active_lag": (None, [f, f, f, vp, vp]),
         "iirdes_pll_active_PI": (None, [f, f, f, vp, vp]),
@@ -980,6 +1010,18 @@ class IirFilt(_Obj):
         return cls.construct("_create_sos", (ptr(B), ptr(A), len(B) // 3), t=t, _b=B, _a=A)
 
     @classmethod
+    def prototype(cls, t, ftype, btype, fmt, order, fc, f0=0.0, Ap=0.1, As=60.0):
+        """the liquid_iirdes design (names or LIQUID_IIRDES_* codes) handed to create_sos (sos) or
+        create (tf): what the reference's create_prototype does, which the library does not export"""
+        B, A = iirdes(ftype, btype, fmt, order, fc, f0, Ap, As)
+        return cls.sos(t, B, A) if _iirdes_codes(ftype, btype, fmt)[2] == 0 else cls(t, B, A)
+
+    @classmethod
+    def lowpass(cls, t, order, fc):
+        """Butterworth low-pass, SOS form (the reference's create_lowpass)"""
+        return cls.prototype(t, "butter", "lowpass", "sos", order, fc, 0.0, 0.1, 60.0)
+
+    @classmethod
     def dc_blocker(cls, t, alpha):
         return cls.construct("_create_dc_blocker", (alpha,), t=t)
 
@@ -1029,6 +1071,153 @@ class IirFilt(_Obj):
 
     def groupdelay(self, fc):
         return float(self._fn("_groupdelay")(self.q, fc))
+
+
+IIRDES_FILTERTYPES = {"butter": 0, "cheby1": 1, "cheby2": 2, "ellip": 3, "bessel": 4}
+IIRDES_BANDTYPES = {"lowpass": 0, "highpass": 1, "bandpass": 2, "bandstop": 3}
+IIRDES_FORMATS = {"sos": 0, "tf": 1}
+
+
+def _iirdes_codes(ftype, btype, fmt):
+    return (IIRDES_FILTERTYPES[ftype] if isinstance(ftype, str) else int(ftype),
+            IIRDES_BANDTYPES[btype] if isinstance(btype, str) else int(btype),
+            IIRDES_FORMATS[fmt] if isinstance(fmt, str) else int(fmt))
+
+
+class _IirRate(_Obj):
+    """iirdecim_<t> / iirinterp_<t>: IirDecim(t, M, b, a) is create; the
+    classmethods default(t, M, order) and prototype(t, M, ...) are the other
+    constructors.  Host arrays through execute / execute_block, device
+    pointers through execute_block_dev (n counted as for execute_block)."""
+
+    def __init__(self, t, M, b, a):
+        self.t, self.M = t, int(M)
+        self.prefix = self.family % t
+        self._b, self._a = _coefs(b, t), _coefs(a, t)
+        self.q = self._fn("_create")(self.M, ptr(self._b), len(self._b), ptr(self._a), len(self._a))
+
+    @classmethod
+    def default(cls, t, M, order):
+        return cls.construct("_create_default", (M, order), t=t, M=int(M))
+
+    @classmethod
+    def prototype(cls, t, M, ftype, btype, fmt, order, fc, f0=0.0, Ap=0.1, As=60.0):
+        return cls.construct("_create_prototype", (M,) + _iirdes_codes(ftype, btype, fmt) + (order, fc, f0, Ap, As),
+                             t=t, M=int(M))
+
+    @property
+    def device_eligible(self):
+        return bool(self._fn("_device_eligible")(self.q))
+
+    def reset(self):
+        self._fn("_reset")(self.q)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
+
+    def groupdelay(self, fc):
+        return float(self._fn("_groupdelay")(self.q, fc))
+
+    def execute_block_dev(self, dx, n, dy):
+        self._fn("_execute_block_dev")(self.q, dx, n, dy)
+
+
+class IirDecim(_IirRate):
+    family = "iirdecim_%s"
+
+    def execute(self, x):
+        """M samples -> one"""
+        x = _samples(x, self.t)
+        assert len(x) == self.M
+        y = np.zeros(1, _out_dtype(self.t))
+        self._fn("_execute")(self.q, ptr(x), ptr(y))
+        return y[0]
+
+    def execute_block(self, x):
+        """n M samples -> n"""
+        x = _samples(x, self.t)
+        assert len(x) % self.M == 0
+        y = np.zeros(len(x) // self.M, _out_dtype(self.t))
+        self._fn("_execute_block")(self.q, ptr(x), len(y), ptr(y))
+        return y
+
+
+class IirInterp(_IirRate):
+    family = "iirinterp_%s"
+
+    def execute(self, v):
+        """one sample -> M"""
+        y = np.zeros(self.M, _out_dtype(self.t))
+        self._fn("_execute")(self.q, _by_value(v, self.t), ptr(y))
+        return y
+
+    def execute_block(self, x):
+        """n samples -> n M"""
+        x = _samples(x, self.t)
+        y = np.zeros(len(x) * self.M, _out_dtype(self.t))
+        self._fn("_execute_block")(self.q, ptr(x), len(x), ptr(y))
+        return y
+
+
+def iirdes(ftype, btype, fmt, order, fc, f0=0.0, Ap=0.1, As=60.0):
+    """liquid_iirdes -> (B, A): 3 coefficients per section (sos) or N + 1
+    each (tf), N the order, doubled for band-pass and band-stop"""
+    ft, bt, fm = _iirdes_codes(ftype, btype, fmt)
+    N = 2 * order if bt >= 2 else order
+    n = 3 * ((N + 1) // 2) if fm == 0 else N + 1
+    B, A = np.zeros(n, np.float32), np.zeros(n, np.float32)
+    lib().liquid_iirdes(ft, bt, fm, order, fc, f0, Ap, As, ptr(B), ptr(A))
+    return B, A
+
+
+def _azpk(fn, n, nz, *args):
+    z, p, k = np.zeros(max(nz, 1), np.complex64), np.zeros(n, np.complex64), np.zeros(1, np.complex64)
+    getattr(lib(), fn)(n, *args, ptr(z), ptr(p), ptr(k))
+    return z[:nz], p, complex(k[0])
+
+
+def butter_azpkf(n):
+    """-> (zeros, poles, gain) of the analog prototype"""
+    return _azpk("butter_azpkf", n, 0)
+
+
+def cheby1_azpkf(n, ep):
+    return _azpk("cheby1_azpkf", n, 0, ep)
+
+
+def cheby2_azpkf(n, es):
+    return _azpk("cheby2_azpkf", n, 2 * (n // 2), es)
+
+
+def ellip_azpkf(n, ep, es):
+    return _azpk("ellip_azpkf", n, 2 * (n // 2), ep, es)
+
+
+def bessel_azpkf(n):
+    return _azpk("bessel_azpkf", n, 0)
+
+
+def bilinear_zpkf(za, pa, ka, m):
+    """-> (zd, pd, kd), len(pa) each"""
+    za, pa = np.ascontiguousarray(za, np.complex64), np.ascontiguousarray(pa, np.complex64)
+    zd, pd, kd = np.zeros(len(pa), np.complex64), np.zeros(len(pa), np.complex64), np.zeros(1, np.complex64)
+    zin = za if len(za) else np.zeros(1, np.complex64)
+    lib().bilinear_zpkf(ptr(zin), len(za), ptr(pa), len(pa), cfloat(float(np.real(ka)), float(np.imag(ka))), m,
+                        ptr(zd), ptr(pd), ptr(kd))
+    return zd, pd, complex(kd[0])
+
+
+def iirdes_isstable(b, a):
+    b, a = np.ascontiguousarray(b, np.float32), np.ascontiguousarray(a, np.float32)
+    assert len(b) == len(a)
+    return bool(lib().iirdes_isstable(ptr(b), ptr(a), len(a)))
+
+
+def liquid_cplxpair(z, tol):
+    z = np.ascontiguousarray(z, np.complex64)
+    p = np.zeros(len(z), np.complex64)
+    lib().liquid_cplxpair(ptr(z), len(z), tol, ptr(p))
+    return p
 
 
 def iirdes_pll_active_lag(w, zeta, K):

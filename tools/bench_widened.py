@@ -6,7 +6,7 @@ objects' stream (20 warm-up + 30 timed calls), samples/s and algorithmic
 GB/s (bytes stated per workload) as a fraction of the 8 TB/s spec.
     python tools/bench_widened.py > gpurun_out/widened.json
     python tools/bench_widened.py --halfband      (the resamp2 / firhilbf / msresamp rows alone)
-    python tools/bench_widened.py --iir           (the iirfilt rows alone)
+    python tools/bench_widened.py --iir           (the iirfilt, iirdecim and iirinterp rows alone)
 """
 import json
 import os
@@ -120,6 +120,7 @@ def iir_rows(L):
         ms = timed(lambda: q.execute_block_dev(x.data_ptr(), n, x.data_ptr()))
         report(name, ms, n, "samples", 16 * n, "16 B/sample algorithmic (24 B/sample moved)")
         q.destroy()
+    iir_rate_rows(x, n)
     del x
     nh = 1 << 20
     xh = (np.random.default_rng(1).uniform(-0.5, 0.5, 2 * nh).astype(np.float32)).view(np.complex64)
@@ -142,6 +143,54 @@ def iir_rows(L):
             q.destroy()
         print(json.dumps(dict({"workload": name + ", 2^20 samples, host pointers, wall clock"}, **res)))
         sys.stdout.flush()
+
+
+def iir_rate_rows(x, n):
+    """iirdecim_crcf / iirinterp_crcf at n full-rate samples in device memory, M = 2, 4, 16, a
+    one-section filter (the DC blocker's size) and Butterworth 8 (create_default: 4 sections), each
+    measured fused (the object) and composed as it could be before these objects existed:
+    IirFilt.execute_block_dev plus a torch strided copy (decimator) or a zero-stuff (interpolator).
+    Bytes per full-rate sample by count: fused decimator 16 + 8/M, fused interpolator 8 + 16/M,
+    composed decimator 32 + 8/M, composed interpolator 32 + 16/M."""
+    full = torch.empty(2 * n, device="cuda")
+    y = torch.empty(2 * n, device="cuda")
+    one_b, one_a = [1.0, -1.0], [1.0, -0.99]
+    for M in (2, 4, 16):
+        m = n // M
+        for fname, rate, plain in (
+                ("1 section", lambda c: c("crcf", M, one_b, one_a), lambda: LQ.IirFilt("crcf", one_b, one_a)),
+                ("butter 8 (4 sections)", lambda c: c.default("crcf", M, 8),
+                 lambda: LQ.IirFilt.lowpass("crcf", 8, 0.5 / M))):
+            d, i, f = rate(LQ.IirDecim), rate(LQ.IirInterp), plain()
+            for q in (d, i, f):
+                assert q.device_eligible
+                q.set_stream(S)
+            ms = timed(lambda: d.execute_block_dev(x.data_ptr(), m, y.data_ptr()))
+            report("iirdecim_crcf M=%d %s, fused" % (M, fname), ms, n, "input samples", 16 * n + 8 * m,
+                   "16 + 8/M B per input sample")
+
+            def composed_decim():
+                f.execute_block_dev(x.data_ptr(), n, full.data_ptr())
+                with torch.cuda.stream(STREAM):
+                    y.view(-1, 2)[:m].copy_(full.view(-1, 2)[::M])
+            ms = timed(composed_decim)
+            report("iirdecim_crcf M=%d %s, composed (iirfilt + strided copy)" % (M, fname), ms, n, "input samples",
+                   32 * n + 8 * m, "32 + 8/M B per input sample")
+            ms = timed(lambda: i.execute_block_dev(x.data_ptr(), m, y.data_ptr()))
+            report("iirinterp_crcf M=%d %s, fused" % (M, fname), ms, n, "output samples", 8 * n + 16 * m,
+                   "8 + 16/M B per output sample")
+
+            def composed_interp():
+                with torch.cuda.stream(STREAM):
+                    full.zero_()
+                    full.view(-1, 2)[::M] = x.view(-1, 2)[:m]
+                f.execute_block_dev(full.data_ptr(), n, y.data_ptr())
+            ms = timed(composed_interp)
+            report("iirinterp_crcf M=%d %s, composed (zero-stuff + iirfilt)" % (M, fname), ms, n, "output samples",
+                   32 * n + 16 * m, "32 + 16/M B per output sample")
+            for q in (d, i, f):
+                q.destroy()
+    del full, y
 
 
 def main():
