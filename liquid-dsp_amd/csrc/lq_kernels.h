@@ -198,7 +198,7 @@ void lqk_fftfilt_make_H(const void *h_dev, unsigned int hlen, int is_complex, un
  * c*LQK_RS_CK and K = outputs emitted by the plan's inputs before it; the
  * state at any other input is the checkpoint before it stepped forward
  * (< LQK_RS_CK inputs).  Power-of-two bank counts store (tau, K) -- the rest
- * of the state is a function of tau there (host/resamp.c) -- other bank
+ * of the state is a function of tau there (host/resamp_plan.c) -- other bank
  * counts the whole state (tau, mu, b, state; bst = b*2 + (state == INTERP)).
  * Inputs g >= pre repeat with period P (Q outputs per period): state(g) =
  * state(pre + (g-pre) % P), K += Q per period; positions beyond `end` are

@@ -12,6 +12,7 @@
 #ifndef LQ_HOST_H
 #define LQ_HOST_H
 
+#include <math.h>
 #include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -204,6 +205,113 @@ int lq_iir_rate_eligible(lq_iir *q, unsigned int M);
 lq_ctx *lq_iir_ctx(lq_iir *q);
 void lq_iir_run_rate(lq_iir *q, int mode, unsigned int M, const void *x, unsigned long long n, void *y, int small);
 void lq_iir_run_rate_dev(lq_iir *q, int mode, unsigned int M, const void *dx, unsigned long long n, void *dy);
+
+/* ---- the resampler's timing plan (host/resamp_plan.c): float32 timing
+ * arithmetic only -- no runtime call, no kernel launch, libc and libm alone */
+enum { RS_BOUNDARY = 0, RS_INTERP = 1 };
+enum { RS_D3 = 3, RS_D4 = 4 };        /* device table: input checkpoints (k_resamp3) / output plan (k_resamp4) */
+
+typedef struct {
+    float tau, mu;
+    int b, st;
+} rs_state;
+
+static const rs_state rs_initial = {0.0f, 0.0f, 0, RS_INTERP};   /* resamp.c:181-195 */
+
+static inline int rs_eq(const rs_state *a, const rs_state *b)
+{
+    return memcmp(&a->tau, &b->tau, 4) == 0 && memcmp(&a->mu, &b->mu, 4) == 0 && a->b == b->b && a->st == b->st;
+}
+
+/* One input of resamp.c:245-311 with the data path removed, in the three
+ * pieces every user composes; float32 arithmetic exactly as the reference
+ * (the library is compiled with -ffp-contract=off).
+ *
+ * rs_due: is an output due at this state?  resamp.c:254 compares int b with
+ * unsigned npfb: the comparison is unsigned, so a negative b (a BOUNDARY
+ * update that leaves tau < 0, only when del < 1/npfb) ends the input, and
+ * rs_end_input's decrement (unsigned arithmetic there too) keeps b negative
+ * until it wraps modulo 2^32.  An INTERP state at the last bank turns
+ * BOUNDARY and waits for the next input (resamp.c:280-285). */
+static inline int rs_due(rs_state *s, unsigned int npfb)
+{
+    if ((unsigned int)s->b >= npfb) return 0;
+    if (s->st == RS_INTERP && s->b == (int)npfb - 1) {
+        s->st = RS_BOUNDARY;
+        s->b = (int)npfb;
+        return 0;
+    }
+    return 1;
+}
+
+/* advance after an output (resamp.c:352-363) */
+static inline void rs_advance(rs_state *s, float del, unsigned int npfb)
+{
+    s->tau += del;
+    const float bf = s->tau * (float)npfb;
+    s->b = (int)floorf(bf);
+    s->mu = bf - (float)s->b;
+    s->st = RS_INTERP;
+}
+
+/* end the input (resamp.c:305-307) */
+static inline void rs_end_input(rs_state *s, unsigned int npfb)
+{
+    s->tau -= 1.0f;
+    s->b = (int)((unsigned int)s->b - npfb);
+}
+
+/* the whole input; returns its number of outputs */
+static inline unsigned int rs_step(rs_state *s, float del, unsigned int npfb)
+{
+    unsigned int n = 0;
+    while (rs_due(s, npfb)) {
+        n++;
+        rs_advance(s, del, npfb);
+    }
+    rs_end_input(s, npfb);
+    return n;
+}
+
+/* the tau-only form of the timing (resamp_plan.c) holds at this rate */
+int rs_tau_only(float del, unsigned int npfb);
+/* outputs of the next nx inputs from state s */
+unsigned long long rs_count_outputs(rs_state s, float del, unsigned int npfb, unsigned long long nx);
+
+/* A plan: position g counts inputs from `origin`; rs_plan_at gives the state
+ * before input g and K = outputs of the inputs before it.  Periodic plans
+ * cover every g (inputs >= pre repeat every P inputs / Q outputs), direct
+ * plans g <= end.  The device table is dn entries of desz bytes at dtab
+ * (lqk_rs_entry_p2 when p2, else lqk_rs_entry, for dk == RS_D3; lqk_rs4_entry
+ * for RS_D4, whose outputs >= opre repeat every QT outputs / PT inputs,
+ * entries [npre, ..) theirs). */
+typedef struct {
+    float del;
+    unsigned int npfb;
+    int p2;                       /* tau-only timing (rs_tau_only) */
+    int valid, periodic;
+    rs_state origin;
+    lqk_rs_entry *tab;            /* host: state at plan position c * RS_HCK (K lookups) */
+    size_t nck, cap;
+    unsigned long long pre, P, Q, end;
+    int dk;                       /* device table kind (RS_D3 / RS_D4) */
+    unsigned char *dtab;          /* the table, until rs_plan_drop_table */
+    size_t dn, desz;
+    unsigned long long opre, npre, QT, PT;
+} rs_plan;
+
+void rs_plan_init(rs_plan *pl);
+void rs_plan_free(rs_plan *pl);
+void rs_plan_drop_table(rs_plan *pl);   /* the device table's host copy (once uploaded) */
+/* want_d4: record an output plan where the timing allows, else (and as the
+ * fall-back) input checkpoints.  periodic: 1, or 0 if the orbit has no
+ * period within the search limit (nothing is left allocated); direct: the
+ * next nx inputs: 1, 0 if their outputs do not fit 32 bits, -1 if no table
+ * could be made (nothing is left allocated either way) */
+int rs_plan_build_periodic(rs_plan *pl, float del, unsigned int npfb, rs_state origin, int want_d4);
+int rs_plan_build_direct(rs_plan *pl, float del, unsigned int npfb, rs_state origin, unsigned long long nx,
+                         int want_d4);
+rs_state rs_plan_at(const rs_plan *pl, unsigned long long g, unsigned long long *K);
 
 /* arbitrary-rate resampler engine (host/resamp.c), used by msresamp */
 typedef struct lq_rs_s lq_rs;
