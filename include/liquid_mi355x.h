@@ -637,6 +637,54 @@ LQMI_IIRRATE_API(iirinterp_cccf, liquid_float_complex, liquid_float_complex, liq
                  liquid_float_complex)
 
 /* ------------------------------------------------------------------------ */
+/* autocorr (liquid.h:1908-1970): cccf, rrrf                                 */
+/* ------------------------------------------------------------------------ */
+/* Windowed delay autocorrelation: after each sample n,
+     rxx[n] = sum_{k=n-W+1..n} x[k] conj(x[k-d])      (rrrf: x[k] x[k-d])
+   with W = _window_size >= 1, d = _delay >= 0 (W + d < 2^31) and zero samples
+   before the last reset.  Every output is one float32 sum of the W products of
+   its own window -- in the kernel too, whose cost per output does not grow
+   with W (csrc/k_autocorr.hip) -- so its error is proportional to the samples
+   it sees.  push, execute and the block calls may be mixed in any order;
+   execute without a new push returns the same value again; _rxx == _x is
+   allowed in execute_block.
+   get_energy is the float32 sum of |x|^2 over the last W samples, computed
+   when asked.  It does not replay the reference's running accumulator
+   (autocorr.c:123-127: add the newest, subtract the oldest), whose rounding
+   error grows over the life of the stream: the two differ by that drift.
+   Extensions: execute_block_dev takes device pointers; _de2 may be NULL, else
+   it receives e2[n] = sum_{k=n-W+1..n} |x[k]|^2 per sample; the input range
+   must not overlap either output range (unlike the host-pointer
+   execute_block, which allows _rxx == _x).  device_eligible: block calls run
+   on the GPU (W <= liquid_mi355x_autocorr_max_window()), else in a host loop.
+   The delay is not limited beyond W + d < 2^31: it only sets the length of
+   the history.  push, execute and get_energy follow the small-call rule
+   (liquid_mi355x_set_small_calls). */
+#define LQMI_AUTOCORR_API(AUTOCORR, TO, TC, TI)                                                 \
+    typedef struct AUTOCORR##_s *AUTOCORR;                                                      \
+    AUTOCORR AUTOCORR##_create(unsigned int _window_size, unsigned int _delay);                 \
+    void AUTOCORR##_destroy(AUTOCORR _q);                                                       \
+    void AUTOCORR##_reset(AUTOCORR _q);                                                         \
+    void AUTOCORR##_print(AUTOCORR _q);                                                         \
+    void AUTOCORR##_push(AUTOCORR _q, TI _x);                                                   \
+    void AUTOCORR##_execute(AUTOCORR _q, TO *_rxx);                                             \
+    void AUTOCORR##_execute_block(AUTOCORR _q, TI *_x, unsigned int _n, TO *_rxx);              \
+    float AUTOCORR##_get_energy(AUTOCORR _q);                                                   \
+    void AUTOCORR##_execute_block_dev(AUTOCORR _q, const TI *_dx, unsigned long long _n,        \
+                                      TO *_drxx, float *_de2);                                  \
+    int AUTOCORR##_device_eligible(AUTOCORR _q);                                                \
+    void AUTOCORR##_set_stream(AUTOCORR _q, void *_hip_stream);                                 \
+    void AUTOCORR##_synchronize(AUTOCORR _q);
+
+LQMI_AUTOCORR_API(autocorr_cccf, liquid_float_complex, liquid_float_complex, liquid_float_complex)
+LQMI_AUTOCORR_API(autocorr_rrrf, float, float, float)
+
+/* extension: outputs per workgroup of the block kernel, and the largest
+   window it takes */
+unsigned int liquid_mi355x_autocorr_tile(void);
+unsigned int liquid_mi355x_autocorr_max_window(void);
+
+/* ------------------------------------------------------------------------ */
 /* fftfilt (liquid.h:2192-2240): rrrf, crcf, cccf                            */
 /* ------------------------------------------------------------------------ */
 #define LQMI_FFTFILT_API(FFTFILT, TO, TC, TI)                                                   \
@@ -718,7 +766,8 @@ const char *liquid_mi355x_build_target(void);
 /* Small-call mode (no reference counterpart).  1 (default): the
  * single-sample / single-vector entry points -- firfilt_*_execute after push,
  * dotprod_*_execute / _run / _run4, firdecim_*_execute, firinterp_*_execute,
- * resamp_*_execute, and fftfilt_*_execute when n * h_len <= 65536 -- compute
+ * resamp_*_execute, autocorr_*_push / _execute / _get_energy, and
+ * fftfilt_*_execute when n * h_len <= 65536 -- compute
  * on the host (host/lq_small.c); every *_execute_block[_dev] call, the
  * channelizers, FFT plans and spgram run on the GPU.  0: every call runs on
  * the GPU.  The environment variable LQ_SMALL_CALLS=gpu sets 0 at load. */

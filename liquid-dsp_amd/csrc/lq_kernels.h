@@ -374,6 +374,25 @@ void lqk_iirfilt_decim(int kind, unsigned int nsec, const void *coef, const void
 void lqk_iirfilt_interp(int kind, unsigned int nsec, const void *coef, const void *ladder, void *state, const void *x,
                         unsigned long long n_in, unsigned int M, void *y, void *work, void *stream);
 
+/* ---------------------------------------------------------------- autocorr (k_autocorr.hip)
+ * rxx[i] = sum_{k=i-W+1..i} s[k] conj(s[k-d]) (cx; else s[k] s[k-d]) and, when
+ * e2 is not NULL, e2[i] = sum_{k=i-W+1..i} |s[k]|^2, i < n, over the stream
+ * s = hist ++ x: hist holds the H = W + d samples before x, oldest first (the
+ * block outputs read the last H - 1 of them; the single output below reads all).
+ * Every output is the sum of its own W terms and of nothing else.  hist_new
+ * receives the last H samples of s (must not alias hist).  x must not overlap
+ * rxx or e2.  1 <= W <= LQK_AUTOCORR_MAXW, W + d < 2^31.
+ * LQK_AUTOCORR_TILE: outputs per workgroup. */
+#define LQK_AUTOCORR_TILE 2048
+#define LQK_AUTOCORR_MAXW 4096
+void lqk_autocorr(int cx, unsigned int W, unsigned long long d, const void *hist, const void *x,
+                  unsigned long long n, void *rxx, float *e2, void *hist_new, void *stream);
+/* the output at the last sample of hist: out = rxx (1 or 2 floats), then e2;
+ * any W.  With a flag, out is pinned host memory and the kernel raises
+ * *flag = seq once it is visible to the host; flag may be NULL. */
+void lqk_autocorr_single(int cx, unsigned int W, unsigned long long d, const void *hist, float *out,
+                         unsigned *flag, unsigned seq, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -329,6 +329,25 @@ def _declare(L):
         "liquid_mi355x_iirfilt_tile": (u, []),
         "liquid_mi355x_iirfilt_scan": (u, []),
     })
+    for t in (CCCF, RRRF):
+        sig.update({
+            "autocorr_%s_create" % t: (vp, [u, u]),
+            "autocorr_%s_destroy" % t: (None, [vp]),
+            "autocorr_%s_reset" % t: (None, [vp]),
+            "autocorr_%s_print" % t: (None, [vp]),
+            "autocorr_%s_push" % t: (None, [vp, f if t == RRRF else cfloat]),
+            "autocorr_%s_execute" % t: (None, [vp, vp]),
+            "autocorr_%s_execute_block" % t: (None, [vp, vp, u, vp]),
+            "autocorr_%s_get_energy" % t: (f, [vp]),
+            "autocorr_%s_execute_block_dev" % t: (None, [vp, vp, ull, vp, vp]),
+            "autocorr_%s_device_eligible" % t: (i, [vp]),
+            "autocorr_%s_set_stream" % t: (None, [vp, vp]),
+            "autocorr_%s_synchronize" % t: (None, [vp]),
+        })
+    sig.update({
+        "liquid_mi355x_autocorr_tile": (u, []),
+        "liquid_mi355x_autocorr_max_window": (u, []),
+    })
     for d in FIRDES_DESIGNS:
         sig["liquid_firdes_" + d] = (None, [u, u, f, f, vp])
     sig.update({
@@ -1071,6 +1090,53 @@ class IirFilt(_Obj):
 
     def groupdelay(self, fc):
         return float(self._fn("_groupdelay")(self.q, fc))
+
+
+class AutoCorr(_Obj):
+    """autocorr_<kind>: windowed delay autocorrelation, kind "cccf" or "rrrf".
+    rxx[n] = sum_{k=n-W+1..n} x[k] conj(x[k-d]); block calls run on the GPU when
+    device_eligible (window <= MAX_WINDOW), else in the library's host loop."""
+    family = "autocorr_%s"
+    TILE = _LibConst("liquid_mi355x_autocorr_tile")               # outputs per workgroup
+    MAX_WINDOW = _LibConst("liquid_mi355x_autocorr_max_window")   # the largest window the kernel takes
+
+    def __init__(self, kind, window, delay):
+        assert kind in (CCCF, RRRF)
+        self.t, self.window, self.delay = kind, int(window), int(delay)
+        self.prefix = self.family % kind
+        self.q = self._fn("_create")(self.window, self.delay)
+
+    @property
+    def device_eligible(self):
+        return bool(self._fn("_device_eligible")(self.q))
+
+    def reset(self):
+        self._fn("_reset")(self.q)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
+
+    def push(self, v):
+        self._fn("_push")(self.q, _by_value(v, self.t))
+
+    def execute(self):
+        y = np.zeros(1, _out_dtype(self.t))
+        self._fn("_execute")(self.q, ptr(y))
+        return y[0]
+
+    def execute_block(self, x, inplace=False):
+        """rxx of the samples x; inplace: the library writes over its input array"""
+        x = _samples(x, self.t)
+        y = x.copy() if inplace else np.zeros(len(x), _out_dtype(self.t))
+        self._fn("_execute_block")(self.q, ptr(y) if inplace else ptr(x), len(x), ptr(y))
+        return y
+
+    def execute_block_dev(self, dx, n, drxx, de2=0):
+        """device pointers; de2 = 0: no energy output"""
+        self._fn("_execute_block_dev")(self.q, dx, n, drxx, de2 or None)
+
+    def get_energy(self):
+        return float(self._fn("_get_energy")(self.q))
 
 
 IIRDES_FILTERTYPES = {"butter": 0, "cheby1": 1, "cheby2": 2, "ellip": 3, "bessel": 4}

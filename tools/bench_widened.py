@@ -7,6 +7,7 @@ GB/s (bytes stated per workload) as a fraction of the 8 TB/s spec.
     python tools/bench_widened.py > gpurun_out/widened.json
     python tools/bench_widened.py --halfband      (the resamp2 / firhilbf / msresamp rows alone)
     python tools/bench_widened.py --iir           (the iirfilt, iirdecim and iirinterp rows alone)
+    python tools/bench_widened.py --autocorr      (the autocorr rows alone)
 """
 import json
 import os
@@ -193,8 +194,56 @@ def iir_rate_rows(x, n):
     del full, y
 
 
+def autocorr_rows(L):
+    """autocorr_cccf, 2^26 samples in device memory, (W, d) = (64, 32), (1024, 1024), (4096, 1), without
+    and with the e2 output: 16 B/sample (8 in, 8 out), 20 with e2.  Beside each shape the same result
+    composed from what the library had before the object: a torch product x[d:] conj(x[:-d]) and a
+    FirFilt("crcf", ones(W)) over it (24 B/sample for the product, 16 for the filter).  Last, the time of the
+    W = 4096 row over the W = 64 row next to the growth the design predicts, the ratio of their halo
+    ratios (TILE + W - 1) / TILE."""
+    import numpy as np
+    n = 1 << 26
+    x = cbuf(n)
+    y = torch.empty(2 * n, device="cuda")
+    e2 = torch.empty(n, device="cuda")
+    prod = torch.empty(2 * n, device="cuda")
+    xc, pc = torch.view_as_complex(x.view(-1, 2)), torch.view_as_complex(prod.view(-1, 2))
+    tile = LQ.AutoCorr.TILE
+    ms_of = {}
+    for W, d in ((64, 32), (1024, 1024), (4096, 1)):
+        q = LQ.AutoCorr("cccf", W, d)
+        assert q.device_eligible
+        q.set_stream(S)
+        for with_e2 in (False, True):
+            ms = timed(lambda: q.execute_block_dev(x.data_ptr(), n, y.data_ptr(), e2.data_ptr() if with_e2 else 0))
+            report("autocorr_cccf W=%d d=%d%s" % (W, d, " + e2" if with_e2 else ""), ms, n, "samples",
+                   (20 if with_e2 else 16) * n, "20 B/sample" if with_e2 else "16 B/sample")
+            ms_of[(W, with_e2)] = ms
+        q.destroy()
+        f = LQ.FirFilt("crcf", np.ones(W, np.float32))
+        f.set_stream(S)
+
+        def composed():
+            with torch.cuda.stream(STREAM):
+                torch.mul(xc[d:], xc[:n - d].conj(), out=pc[:n - d])
+            f.execute_block_dev(prod.data_ptr(), n - d, y.data_ptr())
+        ms = timed(composed, it=5, w=2)
+        report("autocorr_cccf W=%d d=%d, composed (torch product + firfilt_crcf of ones)" % (W, d), ms, n, "samples",
+               40 * n, "24 B/sample product + 16 B/sample filter")
+        f.destroy()
+    halo = lambda W: (tile + W - 1) / tile  # noqa: E731
+    print(json.dumps({"workload": "autocorr_cccf W=4096 over W=64", "time_ratio": round(ms_of[(4096, False)] / ms_of[(64, False)], 3),
+                      "time_ratio_with_e2": round(ms_of[(4096, True)] / ms_of[(64, True)], 3),
+                      "halo_ratio_W4096": round(halo(4096), 3), "halo_ratio_W64": round(halo(64), 3),
+                      "predicted_growth": round(halo(4096) / halo(64), 3)}))
+    sys.stdout.flush()
+
+
 def main():
     L = LQ.lib()
+    if "--autocorr" in sys.argv[1:]:
+        autocorr_rows(L)
+        return
     if "--iir" in sys.argv[1:]:
         iir_rows(L)
         return
@@ -335,6 +384,7 @@ def main():
     del x, y
     halfband_rows(L)
     iir_rows(L)
+    autocorr_rows(L)
     # FFT API batches
     for N in (256, 512, 1024, 2048, 4096, 8192, 16384, 65536, 12345):
         B = (1 << 26) // N
