@@ -773,6 +773,28 @@ const char *liquid_mi355x_build_target(void);
  * the GPU.  The environment variable LQ_SMALL_CALLS=gpu sets 0 at load. */
 void liquid_mi355x_set_small_calls(int _host);
 int liquid_mi355x_get_small_calls(void);
+/* Workgroup limit (no reference counterpart; for tests).  The persistent
+ * kernels launch min(tiles, cap) workgroups and each walks further tiles;
+ * _n > 0 launches at most _n, so a short call walks many tiles per
+ * workgroup.  0 (default): no limit.  Results do not depend on it. */
+void liquid_mi355x_set_max_workgroups(unsigned int _n);
+unsigned int liquid_mi355x_get_max_workgroups(void);
+/* Which kernel a firdecim device call of _nout outputs takes (_kind: 0 rrrf,
+ * 1 crcf, 2 cccf; _x_aligned16: the input pointer is 16-byte aligned), and
+ * the outputs per tile and the grid cap of that launch (0: not capped). */
+enum {
+    LIQUID_MI355X_FIRDECIM_PF_R4X128 = 0, /* persistent, 4 outputs per lane, 128 lanes */
+    LIQUID_MI355X_FIRDECIM_PF_R2X256 = 1, /* persistent, 2 per lane, 256 lanes */
+    LIQUID_MI355X_FIRDECIM_PH2 = 2,       /* one-shot, 2 per lane, 256 lanes */
+    LIQUID_MI355X_FIRDECIM_PF_R1X256 = 3, /* persistent, 1 per lane, 256 lanes */
+    LIQUID_MI355X_FIRDECIM_PH_R1X64 = 4,  /* one-shot, 1 per lane, 64 lanes */
+    LIQUID_MI355X_FIRDECIM_PLAIN = 5,     /* one-shot, undivided taps, 256 lanes */
+    LIQUID_MI355X_FIRDECIM_REFUSED = 6    /* M and filter length past the GPU tile limit */
+};
+int liquid_mi355x_firdecim_route(int _kind, unsigned int _M, unsigned int _h_len, int _x_aligned16,
+                                 unsigned long long _nout);
+unsigned int liquid_mi355x_firdecim_tile(int _route);
+unsigned int liquid_mi355x_firdecim_grid_cap(int _kind, unsigned int _M, unsigned int _h_len, int _route);
 
 #ifdef __cplusplus
 }

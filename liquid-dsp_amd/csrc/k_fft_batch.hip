@@ -410,7 +410,7 @@ void launch_fftsmall(const void *x, void *y, long long batch, int dir, float s1,
 {
     constexpr int G = 256 / R;
     const long long gb = (batch + G - 1) / G;
-    const unsigned grid = (unsigned)(gb < 4096 ? gb : 4096);
+    const unsigned grid = lqrt_grid((unsigned long long)gb, 4096);
     lq_switch<+1, -1>(dir > 0 ? +1 : -1, [&](auto d) {
         hipLaunchKernelGGL((k_fftsmall_batch<R, d>), dim3(grid), dim3(256), 0, st, (const float2 *)x, (float2 *)y,
                            batch, s1, s2, u1, u2, (const float2 *)lqrt_twiddles());
@@ -424,7 +424,7 @@ void launch_fftr16(const void *x, void *y, long long batch, int dir, float s1, f
 {
     constexpr int G = 16 / R;
     const long long g = (batch + G - 1) / G;
-    const unsigned grid = (unsigned)(g < 2048 ? g : 2048);
+    const unsigned grid = lqrt_grid((unsigned long long)g, 2048);
     lq_switch<+1, -1>(dir > 0 ? +1 : -1, [&](auto d) {
         hipLaunchKernelGGL((k_fftr16_batch<R, d>), dim3(grid), dim3(256), 0, st, (const float2 *)x, (float2 *)y,
                            batch, s1, s2, u1, u2, (const float2 *)lqrt_twiddles());
@@ -447,7 +447,7 @@ void launch_fft1024(const void *x, void *y, long long batch, int dir, float s1, 
                     hipStream_t st)
 {
     const long long g = (batch + 3) / 4;
-    const unsigned grid = (unsigned)(g < 4096 ? g : 4096);
+    const unsigned grid = lqrt_grid((unsigned long long)g, 4096);
     lq_switch<+1, -1>(dir > 0 ? +1 : -1, [&](auto d) {
         hipLaunchKernelGGL(k_fft1024_batch<d>, dim3(grid), dim3(256), 0, st, (const float2 *)x, (float2 *)y, batch,
                            s1, s2, u1, u2, (const float2 *)lqrt_twiddles());
@@ -458,7 +458,7 @@ void launch_fft1024(const void *x, void *y, long long batch, int dir, float s1, 
 void launch_fft4096(const void *x, void *y, long long batch, int dir, float s1, float s2, int u1, int u2,
                     hipStream_t st)
 {
-    const unsigned grid = (unsigned)(batch < 2048 ? batch : 2048);
+    const unsigned grid = lqrt_grid((unsigned long long)batch, 2048);
     lq_switch<+1, -1>(dir > 0 ? +1 : -1, [&](auto d) {
         hipLaunchKernelGGL(k_fft4096_batch<d>, dim3(grid), dim3(256), 0, st, (const float2 *)x, (float2 *)y, batch,
                            s1, s2, u1, u2, (const float2 *)lqrt_twiddles());
@@ -470,7 +470,7 @@ void launch_fft4096(const void *x, void *y, long long batch, int dir, float s1, 
 void launch_fft8192(const void *x, void *y, long long batch, int dir, float s1, float s2, int u1, int u2,
                     hipStream_t st)
 {
-    const unsigned grid = (unsigned)(batch < 2048 ? batch : 2048);
+    const unsigned grid = lqrt_grid((unsigned long long)batch, 2048);
     const bool a16 = ((uintptr_t)x & 15) == 0;
     lq_switch<+1, -1>(dir > 0 ? +1 : -1, [&](auto d) {
         lq_switch<1, 0>(a16, [&](auto a) {
@@ -484,7 +484,7 @@ void launch_fft8192(const void *x, void *y, long long batch, int dir, float s1, 
 void launch_fft16384(const void *x, void *y, long long batch, int dir, float s1, float s2, int u1, int u2,
                      hipStream_t st)
 {
-    const unsigned grid = (unsigned)(batch < 1024 ? batch : 1024);
+    const unsigned grid = lqrt_grid((unsigned long long)batch, 1024);
     const bool a16 = ((uintptr_t)x & 15) == 0;
     lq_switch<+1, -1>(dir > 0 ? +1 : -1, [&](auto d) {
         lq_switch<1, 0>(a16, [&](auto a) {

@@ -304,14 +304,14 @@ extern "C" void lqk_fftfilt_run(int real_io, unsigned int hlen, unsigned int nff
         if (nfft == 8192) {
             const int hd = (hm1 + 1) & ~1;   // discarded outputs per segment: even, >= h - 1
             const long long nsegc = ((long long)nc + (8192 - hd) - 1) / (8192 - hd);
-            const unsigned grid = (unsigned)(nsegc < 768 ? nsegc : 768);   // persistent, three resident per CU
+            const unsigned grid = lqrt_grid((unsigned long long)nsegc, 768);   // persistent, three resident per CU
             const bool a16 = (((uintptr_t)xc | (uintptr_t)yc) & 15) == 0;
             hipLaunchKernelGGL(a16 ? k_fftfilt8k<true> : k_fftfilt8k<false>, dim3(grid), dim3(NT), 0, st, hd, hm1,
                                (const float2 *)H, hc, (const void *)xc, (long long)nc, yc, sre, sim, tw, hj);
         } else {
             const int L = NFFT - hm1;
             const long long nsegc = ((long long)nc + L - 1) / L;
-            const unsigned grid = (unsigned)(nsegc < 4096 ? nsegc : 4096);   // persistent, four resident per CU
+            const unsigned grid = lqrt_grid((unsigned long long)nsegc, 4096);   // persistent, four resident per CU
             if (real_io)
                 hipLaunchKernelGGL((k_fftfilt_r16<true>), dim3(grid), dim3(NT), 0, st, hm1, (const float2 *)H, hc,
                                    (const void *)xc, (long long)nc, yc, sre, sim, tw, hj);

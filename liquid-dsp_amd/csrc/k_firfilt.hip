@@ -880,6 +880,9 @@ void dispatch_firfilt(const lqk_fir_desc *d, const void *hist, const void *x, lo
 
 size_t elem_size(int kind) { return kind == 0 ? sizeof(float) : sizeof(float2); }
 
+// dynamic LDS of the plain k_firdecim: NT outputs' inputs and HP taps' history
+size_t decim_plain_lds(int kind, unsigned M, unsigned HP) { return ((size_t)NT * M + HP) * elem_size(kind); }
+
 } // namespace
 
 extern "C" unsigned int lqk_firfilt_max_history(int kind)
@@ -981,7 +984,7 @@ extern "C" void lqk_firdecim(const lqk_fir_desc *d, unsigned int M, const void *
     hipStream_t st = (hipStream_t)stream;
     const int HP = (int)(d->hc * d->nchunk);
     const unsigned nb = (unsigned)((nout + NT - 1) / NT);
-    const size_t lds = (size_t)(NT * M + HP) * elem_size(d->kind);
+    const size_t lds = decim_plain_lds(d->kind, M, (unsigned)HP);
     if (lds > FIR_LDS_MAX) {
         fprintf(stderr, "error: firdecim: decimation/filter length exceeds the GPU tile limit\n");
         exit(1);
@@ -1017,32 +1020,21 @@ void launch_decim_ph(unsigned M, unsigned QC, const void *hq, unsigned hl1, cons
     LQ_CHECK_LAUNCH();
 }
 
-template <int KIND, int QCT>
-int decim_ph_shape(unsigned M, unsigned QC, const void *hq, unsigned hl1, const void *hist, const void *x,
-                   long long nout, void *y, hipStream_t st)
-{
-    const size_t es = elem_size(KIND);
-    const size_t lds_a = (size_t)M * dph_pitch(256 * 2 + (int)QC - 1) * es;
-    const size_t lds_b = (size_t)M * dph_pitch(64 + (int)QC - 1) * es;
-    if (lds_a <= 64 * 1024) launch_decim_ph<KIND, QCT, 2, 256>(M, QC, hq, hl1, hist, x, nout, y, lds_a, st);
-    else if (lds_b <= FIR_LDS_MAX) launch_decim_ph<KIND, QCT, 1, 64>(M, QC, hq, hl1, hist, x, nout, y, lds_b, st);
-    else return -1;
-    return 0;
-}
-
+// one output per lane on 64 lanes (the route function has checked QC % 4 == 0
+// and the LDS need); the tap chunk QCT by QC
 template <int KIND>
-int decim_ph_qct(unsigned M, unsigned QC, const void *hq, unsigned hl1, const void *hist, const void *x,
-                 long long nout, void *y, hipStream_t st)
+void decim_ph_qct(unsigned M, unsigned QC, const void *hq, unsigned hl1, const void *hist, const void *x,
+                  long long nout, void *y, size_t lds, hipStream_t st)
 {
     switch (QC) {
-    case 4: return decim_ph_shape<KIND, 4>(M, QC, hq, hl1, hist, x, nout, y, st);
-    case 8: return decim_ph_shape<KIND, 8>(M, QC, hq, hl1, hist, x, nout, y, st);
-    case 16: return decim_ph_shape<KIND, 16>(M, QC, hq, hl1, hist, x, nout, y, st);
-    case 32: return decim_ph_shape<KIND, 32>(M, QC, hq, hl1, hist, x, nout, y, st);
+    case 4: launch_decim_ph<KIND, 4, 1, 64>(M, QC, hq, hl1, hist, x, nout, y, lds, st); break;
+    case 8: launch_decim_ph<KIND, 8, 1, 64>(M, QC, hq, hl1, hist, x, nout, y, lds, st); break;
+    case 16: launch_decim_ph<KIND, 16, 1, 64>(M, QC, hq, hl1, hist, x, nout, y, lds, st); break;
+    case 32: launch_decim_ph<KIND, 32, 1, 64>(M, QC, hq, hl1, hist, x, nout, y, lds, st); break;
     default:
-        if (QC % 16 == 0) return decim_ph_shape<KIND, 16>(M, QC, hq, hl1, hist, x, nout, y, st);
-        if (QC % 4 == 0) return decim_ph_shape<KIND, 4>(M, QC, hq, hl1, hist, x, nout, y, st);
-        return -1;
+        if (QC % 16 == 0) launch_decim_ph<KIND, 16, 1, 64>(M, QC, hq, hl1, hist, x, nout, y, lds, st);
+        else launch_decim_ph<KIND, 4, 1, 64>(M, QC, hq, hl1, hist, x, nout, y, lds, st);
+        break;
     }
 }
 } // namespace
@@ -1054,26 +1046,85 @@ extern "C" unsigned lqk_firdecim_ph_qc(unsigned M, unsigned hlen)
 }
 
 namespace {
+// Where a call goes, and the launch arithmetic of that route: the one decision
+// behind lqk_firdecim_route and lqk_firdecim_ph's launches.
+struct decim_plan {
+    int route;       // LQK_DECIM_*
+    size_t lds;      // dynamic LDS of the launch
+    int nl;          // persistent form: 16-byte vectors per lane and tile
+    unsigned tile;   // outputs per workgroup tile
+    unsigned cap;    // persistent form: the grid cap, 256 wpc; else 0
+};
+
 // The persistent prefetching form (k_firdecim_pf) for 16-byte aligned x: R
 // outputs per lane on NTD lanes, TO = R NTD outputs and (TO + QC - 1) M input
-// samples per workgroup in LDS; -1 when the shape does not fit it
+// samples per workgroup in LDS; false when the shape does not fit it
 template <int R, int NTD>
-int decim_pf(int kind, unsigned int M, unsigned int QC, const void *hq, unsigned int hl1, const void *hist,
-             const void *x, unsigned long long nout, void *y, hipStream_t st)
+bool decim_pf_fits(int route, int kind, unsigned M, unsigned QC, bool x16, unsigned long long nout, decim_plan *p)
 {
     constexpr int TO2 = R * NTD;
     const int J = TO2 + (int)QC - 1;
     const size_t lds = (size_t)M * (R * dph2_q<R>(J) + 1) * elem_size(kind);
+    if (!((QC % 4) == 0 && lds <= 40 * 1024 && (unsigned long long)(J) * M < (1u << 24) && x16 &&
+          nout * M * elem_size(kind) < (1ull << 31)))
+        return false;
     const int S = J * (int)M + 1;
     const int vw = 16 / (int)elem_size(kind);
     const int nl = (S + NTD * vw - 1) / (NTD * vw);
-    if (!((QC % 4) == 0 && lds <= 40 * 1024 && (unsigned long long)(J) * M < (1u << 24) &&
-          ((uintptr_t)x & 15) == 0 && nl <= 12 && nout * M * elem_size(kind) < (1ull << 31)))
-        return -1;
-    const unsigned long long nt = (nout + TO2 - 1) / TO2;
+    if (nl > 12) return false;
     const int wpc = (int)((160 * 1024) / lds) < 8 ? (int)((160 * 1024) / lds) : 8;
-    const unsigned nb = (unsigned)(nt < 256ull * wpc ? nt : 256ull * wpc);
-#define LQ_DP(K, NLV)                                                                                      \
+    *p = decim_plan{route, lds, nl, (unsigned)TO2, 256u * (unsigned)wpc};
+    return true;
+}
+
+decim_plan decim_decide(int kind, unsigned M, unsigned QC, unsigned hlen, bool x16, unsigned long long nout)
+{
+    decim_plan p{LQK_DECIM_REFUSED, 0, 0, 0, 0};
+    // the persistent form: at M = 8 (m = 8 crcf, 2^27 inputs: 0.304-0.333 ->
+    // 0.283-0.286 ms against the one-shot form, r05zf) two outputs per lane
+    // on 256 lanes (four per lane on 128: 0.271 -> 0.36 ms); at small M, where
+    // the outputs are many and each is M (QC / 4)(R + 3) / R window reads,
+    // four per lane on 128 lanes (M = 2 / 3 / 4: 0.468 / 0.337 / 0.303 ->
+    // 0.333 / 0.303 / 0.266 ms, r06fd)
+    if (M <= 4 ? decim_pf_fits<4, 128>(LQK_DECIM_PF_R4X128, kind, M, QC, x16, nout, &p)
+               : decim_pf_fits<2, 256>(LQK_DECIM_PF_R2X256, kind, M, QC, x16, nout, &p))
+        return p;
+    {
+        // one-shot form: 512 outputs per workgroup, two per lane, 256 lanes
+        const int J = 512 + (int)QC - 1;
+        const size_t lds = (size_t)M * (2 * dph2_q<2>(J) + 1) * elem_size(kind);
+        if ((QC % 4) == 0 && lds <= 64 * 1024 && (unsigned long long)(J) * M < (1u << 24))
+            return decim_plan{LQK_DECIM_PH2, lds, 0, 512u, 0u};
+    }
+    // longer spans (M >= 16 at 2 M m taps): the persistent form on 256-output
+    // tiles, one output per lane (M = 16 m = 8: 0.479 -> 0.308 ms; at M = 12
+    // the one-shot form above is faster, 0.306 vs 0.366, r06fd)
+    if (decim_pf_fits<1, 256>(LQK_DECIM_PF_R1X256, kind, M, QC, x16, nout, &p)) return p;
+    {
+        // 64 outputs per workgroup.  (A 512-output tile of this layout,
+        // M dph_pitch(511 + QC) elements, is never the choice: whenever it is
+        // within 64 KB the one-shot form above, M (515 + QC) at most, is too.)
+        const size_t lds = (size_t)M * dph_pitch(64 + (int)QC - 1) * elem_size(kind);
+        if ((QC % 4) == 0 && lds <= FIR_LDS_MAX) return decim_plan{LQK_DECIM_PH_R1X64, lds, 0, 64u, 0u};
+    }
+    // the plain kernel's tile, 256 M + hlen samples, is the smaller one only
+    // past about 6000 taps per unit of M (dph_pitch pads a row by 1/32)
+    const size_t lds = decim_plain_lds(kind, M, hlen);
+    if (lds <= FIR_LDS_MAX) return decim_plan{LQK_DECIM_PLAIN, lds, 0, (unsigned)NT, 0u};
+    return p;
+}
+
+template <int R, int NTD>
+void launch_decim_pf(const decim_plan &p, int kind, unsigned int M, unsigned int QC, const void *hq,
+                     unsigned int hl1, const void *hist, const void *x, unsigned long long nout, void *y,
+                     hipStream_t st)
+{
+    constexpr int TO2 = R * NTD;
+    const size_t lds = p.lds;
+    const int nl = p.nl;
+    const unsigned long long nt = (nout + TO2 - 1) / TO2;
+    const unsigned nb = lqrt_grid(nt, p.cap);
+#define LQ_DP(K, NLV)                                                                                    \
     hipLaunchKernelGGL((k_firdecim_pf<K, R, NTD, NLV>), dim3(nb), dim3(NTD), lds, st, (const kt<K>::T *)hist, \
                        (int)hl1, (const kt<K>::T *)x, (long long)nout, (int)M, (int)QC, (kt<K>::T *)y,         \
                        (const kt<K>::TC *)hq);
@@ -1087,53 +1138,77 @@ int decim_pf(int kind, unsigned int M, unsigned int QC, const void *hq, unsigned
 #undef LQ_DPK
 #undef LQ_DP
     LQ_CHECK_LAUNCH();
-    return 0;
+}
+
+void launch_decim_ph2(const decim_plan &p, int kind, unsigned int M, unsigned int QC, const void *hq,
+                      unsigned int hl1, const void *hist, const void *x, unsigned long long nout, void *y,
+                      hipStream_t st)
+{
+    constexpr int LQ_D2R = 2, LQ_D2NT = 256;
+    constexpr int TO2 = LQ_D2R * LQ_D2NT;
+    const size_t lds = p.lds;
+    const unsigned nb = (unsigned)((nout + TO2 - 1) / TO2);
+#define LQ_D2(K)                                                                                          \
+    hipLaunchKernelGGL((k_firdecim_ph2<K, LQ_D2R, LQ_D2NT>), dim3(nb), dim3(LQ_D2NT), lds, st, (const kt<K>::T *)hist, (int)hl1, \
+                       (const kt<K>::T *)x, (long long)nout, (int)M, (int)QC, (kt<K>::T *)y, (const kt<K>::TC *)hq);
+    switch (kind) {
+    case 0: LQ_D2(0) break;
+    case 1: LQ_D2(1) break;
+    default: LQ_D2(2) break;
+    }
+#undef LQ_D2
+    LQ_CHECK_LAUNCH();
 }
 } // namespace
+
+extern "C" int lqk_firdecim_route(int kind, unsigned int M, unsigned int hlen, int x_aligned16,
+                                  unsigned long long nout)
+{
+    if (kind < 0 || kind > 2 || M == 0 || hlen == 0) return LQK_DECIM_REFUSED;
+    return decim_decide(kind, M, lqk_firdecim_ph_qc(M, hlen), hlen, x_aligned16 != 0, nout).route;
+}
+
+extern "C" unsigned int lqk_firdecim_route_tile(int route)
+{
+    switch (route) {
+    case LQK_DECIM_PF_R4X128:
+    case LQK_DECIM_PF_R2X256:
+    case LQK_DECIM_PH2: return 512;
+    case LQK_DECIM_PF_R1X256:
+    case LQK_DECIM_PLAIN: return 256;
+    case LQK_DECIM_PH_R1X64: return 64;
+    default: return 0;
+    }
+}
+
+extern "C" unsigned int lqk_firdecim_route_cap(int kind, unsigned int M, unsigned int hlen, int route)
+{
+    // the plan of a one-output aligned call, which is the route's persistent
+    // form wherever that form fits the shape at all
+    if (kind < 0 || kind > 2 || M == 0 || hlen == 0) return 0;
+    const decim_plan p = decim_decide(kind, M, lqk_firdecim_ph_qc(M, hlen), hlen, true, 1);
+    return p.route == route ? p.cap : 0;
+}
 
 extern "C" int lqk_firdecim_ph(int kind, unsigned int M, unsigned int QC, const void *hq, unsigned int hl1,
                                const void *hist, const void *x, unsigned long long nout, void *y, void *stream)
 {
     if (nout == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
-    // the persistent form: at M = 8 (m = 8 crcf, 2^27 inputs: 0.304-0.333 ->
-    // 0.283-0.286 ms against the one-shot form, r05zf) two outputs per lane
-    // on 256 lanes (four per lane on 128: 0.271 -> 0.36 ms); at small M, where
-    // the outputs are many and each is M (QC / 4)(R + 3) / R window reads,
-    // four per lane on 128 lanes (M = 2 / 3 / 4: 0.468 / 0.337 / 0.303 ->
-    // 0.333 / 0.303 / 0.266 ms, r06fd)
-    if ((M <= 4 ? decim_pf<4, 128>(kind, M, QC, hq, hl1, hist, x, nout, y, st)
-                : decim_pf<2, 256>(kind, M, QC, hq, hl1, hist, x, nout, y, st)) == 0)
-        return 0;
-    {
-        // one-shot form: 512 outputs per workgroup, two per lane, 256 lanes
-        constexpr int LQ_D2R = 2, LQ_D2NT = 256;
-        constexpr int TO2 = LQ_D2R * LQ_D2NT;
-        const int J = TO2 + (int)QC - 1;
-        const size_t lds = (size_t)M * (LQ_D2R * dph2_q<LQ_D2R>(J) + 1) * elem_size(kind);
-        if ((QC % 4) == 0 && lds <= 64 * 1024 && (unsigned long long)(J) * M < (1u << 24)) {
-            const unsigned nb = (unsigned)((nout + TO2 - 1) / TO2);
-#define LQ_D2(K)                                                                                          \
-    hipLaunchKernelGGL((k_firdecim_ph2<K, LQ_D2R, LQ_D2NT>), dim3(nb), dim3(LQ_D2NT), lds, st, (const kt<K>::T *)hist, (int)hl1, \
-                       (const kt<K>::T *)x, (long long)nout, (int)M, (int)QC, (kt<K>::T *)y, (const kt<K>::TC *)hq);
-            switch (kind) {
-            case 0: LQ_D2(0) break;
-            case 1: LQ_D2(1) break;
-            default: LQ_D2(2) break;
-            }
-#undef LQ_D2
-            LQ_CHECK_LAUNCH();
-            return 0;
+    const decim_plan p = decim_decide(kind, M, QC, hl1 + 1, ((uintptr_t)x & 15) == 0, nout);
+    switch (p.route) {
+    case LQK_DECIM_PF_R4X128: launch_decim_pf<4, 128>(p, kind, M, QC, hq, hl1, hist, x, nout, y, st); return 0;
+    case LQK_DECIM_PF_R2X256: launch_decim_pf<2, 256>(p, kind, M, QC, hq, hl1, hist, x, nout, y, st); return 0;
+    case LQK_DECIM_PF_R1X256: launch_decim_pf<1, 256>(p, kind, M, QC, hq, hl1, hist, x, nout, y, st); return 0;
+    case LQK_DECIM_PH2: launch_decim_ph2(p, kind, M, QC, hq, hl1, hist, x, nout, y, st); return 0;
+    case LQK_DECIM_PH_R1X64:
+        switch (kind) {
+        case 0: decim_ph_qct<0>(M, QC, hq, hl1, hist, x, (long long)nout, y, p.lds, st); break;
+        case 1: decim_ph_qct<1>(M, QC, hq, hl1, hist, x, (long long)nout, y, p.lds, st); break;
+        default: decim_ph_qct<2>(M, QC, hq, hl1, hist, x, (long long)nout, y, p.lds, st); break;
         }
-    }
-    // longer spans (M >= 16 at 2 M m taps): the persistent form on 256-output
-    // tiles, one output per lane (M = 16 m = 8: 0.479 -> 0.308 ms; at M = 12
-    // the one-shot form above is faster, 0.306 vs 0.366, r06fd)
-    if (decim_pf<1, 256>(kind, M, QC, hq, hl1, hist, x, nout, y, st) == 0) return 0;
-    switch (kind) {
-    case 0: return decim_ph_qct<0>(M, QC, hq, hl1, hist, x, (long long)nout, y, st);
-    case 1: return decim_ph_qct<1>(M, QC, hq, hl1, hist, x, (long long)nout, y, st);
-    default: return decim_ph_qct<2>(M, QC, hq, hl1, hist, x, (long long)nout, y, st);
+        return 0;
+    default: return -1;   // the plain kernel or none: lqk_firdecim launches or refuses
     }
 }
 

@@ -528,7 +528,7 @@ static void launch_mx(const lqk_fir_desc *d, const void *hist, const void *x, lo
 {
     if (d->kind == 0) {   // rrrf: 4096-output chunks, four workgroups per CU (112 VGPRs, 38 KB of LDS)
         const long long nch = (n + CHR - 1) / CHR;
-        const long long nwg = nch < 1024 ? nch : 1024;
+        const long long nwg = lqrt_grid((unsigned long long)nch, 1024);
         hipLaunchKernelGGL(k_firfilt_mx16_r<4>, dim3((unsigned)nwg), dim3(NT), LDSR16, st, (const float *)hist,
                            (const float *)x, n, (float *)y, (const float *)d->hpad, d->scale_re, nch, (int)d->hlen, hj);
         LQ_CHECK_LAUNCH();
@@ -542,7 +542,7 @@ static void launch_mx(const lqk_fir_desc *d, const void *hist, const void *x, lo
     // crcf h = 128 / 192 / 256 0.555 / 0.71 / 0.85 -> 0.50 / 0.62 / 0.75 ms
     // per 2^27 samples (r05x, r05za in profiles/r05_ab_experiments.txt)
     auto go = [&](auto kern, int wpc, int lds) {
-        const long long g = nch < 256LL * wpc ? nch : 256LL * wpc;
+        const long long g = lqrt_grid((unsigned long long)nch, 256u * (unsigned)wpc);
         hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(NT), lds, st, (const v2f *)hist, (const v2f *)x, n,
                            (v2f *)y, (const float *)d->hpad, d->scale_re, d->scale_im, nch, (int)d->hlen, hj);
     };

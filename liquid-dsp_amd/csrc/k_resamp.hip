@@ -592,7 +592,7 @@ void launch_rs(const lqk_rs_plan &pl, unsigned long long g0, unsigned long long 
             const long long ntiles = (n + tin - 1) / tin;
             const long long wgs = (ntiles + NT3 / 64 - 1) / (NT3 / 64);
             const int blk = lds3 <= 160 * 1024 / RS3_BLK ? RS3_BLK : (int)(160 * 1024 / lds3);
-            const unsigned nb = (unsigned)(wgs < 256 * blk ? wgs : 256 * blk);   // persistent: blk per CU
+            const unsigned nb = lqrt_grid((unsigned long long)wgs, 256u * (unsigned)blk);   // persistent: blk per CU
             if (cst)
                 hipLaunchKernelGGL((k_resamp3<L, S, RSC>), dim3(nb), dim3(NT3), lds3, st, pl, g0, K0, npfb, del,
                                    taps2, hist, x, n, y, (int)nout, tin);

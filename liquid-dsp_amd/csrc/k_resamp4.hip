@@ -573,7 +573,7 @@ void launch_rs4_c(const lqk_rs4_plan &pl, unsigned long long g0, unsigned long l
     const int wgs = (ntiles + NT4 / 64 - 1) / (NT4 / 64);
     constexpr int B = HM ? 4 : rs4_blk<L, UP, DN>();   // the fused stage's window needs the VGPRs of a fifth
     const int blk = lds * B <= 160 * 1024 ? B : (int)(160 * 1024 / lds);
-    const int nb = wgs < 256 * blk ? wgs : 256 * blk;   // persistent: blk per CU
+    const int nb = (int)lqrt_grid((unsigned long long)wgs, 256u * (unsigned)blk);   // persistent: blk per CU
     if (npfb == 64)
         hipLaunchKernelGGL((k_resamp4<L, 64, UP, HM, R4, DN>), dim3(nb), dim3(NT4), lds, st, pl, g0, K0, npfb, del,
                            taps2, hist, x, n, y, nout, smode, hb, hj);

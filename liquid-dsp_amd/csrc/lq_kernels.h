@@ -33,6 +33,9 @@ int    lqrt_is_device_ptr(const void *p);
 const float *lqrt_twiddles(void);               /* W_4096^e = exp(-2 pi i e/4096), e<4096 */
 #define LQRT_ZEROS 256
 const float *lqrt_zeros(void);                  /* LQRT_ZEROS bytes of zeros in device memory */
+/* grid of a persistent launch: min(want, cap), and at most the limit of
+ * liquid_mi355x_set_max_workgroups when one is set (tests only) */
+unsigned lqrt_grid(unsigned long long want, unsigned cap);
 /* small-call completion: one kernel copies `bytes` (a multiple of 4, at most
  * LQRT_COPYOUT_MAX) from device memory src to pinned host memory dst, makes
  * them visible system-wide and then stores `seq` to the pinned word *flag;
@@ -116,6 +119,24 @@ void lqk_firdecim(const lqk_fir_desc *d, unsigned int M, const void *hist, const
 unsigned lqk_firdecim_ph_qc(unsigned M, unsigned hlen);
 int lqk_firdecim_ph(int kind, unsigned int M, unsigned int QC, const void *hq, unsigned int hl1,
                     const void *hist, const void *x, unsigned long long nout, void *y, void *stream);
+/* Which kernel a device call takes: a pure function of the shape, the one
+ * lqk_firdecim_ph itself switches on (hlen -> QC by lqk_firdecim_ph_qc).
+ * PLAIN and REFUSED are the cases where lqk_firdecim_ph returns -1 and
+ * lqk_firdecim launches k_firdecim or exits.  _tile: outputs per workgroup
+ * tile of a route; _cap: the grid cap of a persistent route for this shape
+ * (0 when the shape never takes that route). */
+enum {
+    LQK_DECIM_PF_R4X128 = 0,   /* k_firdecim_pf, 4 outputs per lane, 128 lanes */
+    LQK_DECIM_PF_R2X256 = 1,   /* k_firdecim_pf, 2 per lane, 256 lanes */
+    LQK_DECIM_PH2 = 2,         /* k_firdecim_ph2, 2 per lane, 256 lanes */
+    LQK_DECIM_PF_R1X256 = 3,   /* k_firdecim_pf, 1 per lane, 256 lanes */
+    LQK_DECIM_PH_R1X64 = 4,    /* k_firdecim_ph, 1 per lane, 64 lanes */
+    LQK_DECIM_PLAIN = 5,       /* k_firdecim */
+    LQK_DECIM_REFUSED = 6
+};
+int lqk_firdecim_route(int kind, unsigned int M, unsigned int hlen, int x_aligned16, unsigned long long nout);
+unsigned int lqk_firdecim_route_tile(int route);
+unsigned int lqk_firdecim_route_cap(int kind, unsigned int M, unsigned int hlen, int route);
 void lqk_firinterp(int kind, const void *hpoly /* M x L, h[p + l*M] */, unsigned int M,
                    unsigned int L, float scale_re, float scale_im, const void *hist, const void *x,
                    unsigned long long n, void *y, void *stream);

@@ -162,6 +162,31 @@ extern "C" const float *lqrt_twiddles(void)
 
 extern "C" const float *lqrt_zeros(void) { return lqrt_twiddles() + 2 * LQ_TW_N; }
 
+// ------------------------------------------------------- workgroup limit
+// The persistent kernels cap their grid and let each workgroup walk further
+// tiles.  A limit below the caps makes every workgroup walk many tiles at
+// sizes that take milliseconds; the tests set it, nothing else does (0, the
+// default: no limit, every grid is min(want, cap)).
+static unsigned g_max_workgroups = 0;
+
+extern "C" void liquid_mi355x_set_max_workgroups(unsigned int n)
+{
+    __atomic_store_n(&g_max_workgroups, n, __ATOMIC_RELAXED);
+}
+
+extern "C" unsigned int liquid_mi355x_get_max_workgroups(void)
+{
+    return __atomic_load_n(&g_max_workgroups, __ATOMIC_RELAXED);
+}
+
+extern "C" unsigned lqrt_grid(unsigned long long want, unsigned cap)
+{
+    const unsigned lim = __atomic_load_n(&g_max_workgroups, __ATOMIC_RELAXED);
+    unsigned long long g = want < cap ? want : cap;
+    if (lim && g > lim) g = lim;
+    return (unsigned)g;
+}
+
 // ------------------------------------------------------------ small calls
 // The per-call liquid.h API (firfilt_execute, dotprod_execute,
 // firpfbch2_execute ...) returns only after its result is in host memory.

@@ -210,6 +210,28 @@ static void lq_decim_block(lq_decim *q, const void *x, unsigned long long nout, 
     }                                                                                               \
     void NAME##_set_stream(NAME _q, void *_s) { lq_ctx_set_stream(&_q->e->ctx, _s); }
 
+/* the route query of include/liquid_mi355x.h: the kernels' own decision */
+_Static_assert((int)LIQUID_MI355X_FIRDECIM_PF_R4X128 == (int)LQK_DECIM_PF_R4X128 &&
+               (int)LIQUID_MI355X_FIRDECIM_PF_R2X256 == (int)LQK_DECIM_PF_R2X256 &&
+               (int)LIQUID_MI355X_FIRDECIM_PH2 == (int)LQK_DECIM_PH2 &&
+               (int)LIQUID_MI355X_FIRDECIM_PF_R1X256 == (int)LQK_DECIM_PF_R1X256 &&
+               (int)LIQUID_MI355X_FIRDECIM_PH_R1X64 == (int)LQK_DECIM_PH_R1X64 &&
+               (int)LIQUID_MI355X_FIRDECIM_PLAIN == (int)LQK_DECIM_PLAIN &&
+               (int)LIQUID_MI355X_FIRDECIM_REFUSED == (int)LQK_DECIM_REFUSED, "route codes");
+
+int liquid_mi355x_firdecim_route(int _kind, unsigned int _M, unsigned int _h_len, int _x_aligned16,
+                                 unsigned long long _nout)
+{
+    return lqk_firdecim_route(_kind, _M, _h_len, _x_aligned16, _nout);
+}
+
+unsigned int liquid_mi355x_firdecim_tile(int _route) { return lqk_firdecim_route_tile(_route); }
+
+unsigned int liquid_mi355x_firdecim_grid_cap(int _kind, unsigned int _M, unsigned int _h_len, int _route)
+{
+    return lqk_firdecim_route_cap(_kind, _M, _h_len, _route);
+}
+
 LQ_FIRDECIM_FRONT(firdecim_rrrf, LQ_RRRF, float, float, float)
 LQ_FIRDECIM_FRONT(firdecim_crcf, LQ_CRCF, liquid_float_complex, float, liquid_float_complex)
 LQ_FIRDECIM_FRONT(firdecim_cccf, LQ_CCCF, liquid_float_complex, liquid_float_complex, liquid_float_complex)

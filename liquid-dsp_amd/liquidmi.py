@@ -58,6 +58,37 @@ def get_small_calls():
     return bool(lib().liquid_mi355x_get_small_calls())
 
 
+def set_max_workgroups(n):
+    """Workgroup limit of the persistent kernels (include/liquid_mi355x.h):
+    n > 0 launches at most n workgroups, so each walks many tiles; 0 (the
+    default) removes the limit.  For tests."""
+    lib().liquid_mi355x_set_max_workgroups(int(n))
+
+
+def get_max_workgroups():
+    return int(lib().liquid_mi355x_get_max_workgroups())
+
+
+# liquid_mi355x_firdecim_route's codes, by name
+FIRDECIM_ROUTES = ("pf_r4x128", "pf_r2x256", "ph2", "pf_r1x256", "ph_r1x64", "plain", "refused")
+_KINDS = {"rrrf": 0, "crcf": 1, "cccf": 2}
+
+
+def firdecim_route(t, M, hlen, aligned16=True, nout=1):
+    """The kernel a firdecim device call of nout outputs takes (no GPU call)."""
+    return FIRDECIM_ROUTES[lib().liquid_mi355x_firdecim_route(_KINDS[t], M, hlen, 1 if aligned16 else 0, nout)]
+
+
+def firdecim_tile(route):
+    """Outputs per workgroup tile of a route."""
+    return int(lib().liquid_mi355x_firdecim_tile(FIRDECIM_ROUTES.index(route)))
+
+
+def firdecim_grid_cap(t, M, hlen, route):
+    """Grid cap of a persistent route at this shape (0: the shape never takes it)."""
+    return int(lib().liquid_mi355x_firdecim_grid_cap(_KINDS[t], M, hlen, FIRDECIM_ROUTES.index(route)))
+
+
 def header_functions():
     """Every function the public header declares (macros expanded by cpp)."""
     out = subprocess.check_output(["gcc", "-E", "-P", "-I", os.path.join(ROOT, "include"), HEADER],
@@ -359,6 +390,11 @@ def _declare(L):
         "liquid_mi355x_memcpy_h2d": (None, [vp, vp, ull]),
         "liquid_mi355x_memcpy_d2h": (None, [vp, vp, ull]),
         "liquid_mi355x_device_synchronize": (None, []),
+        "liquid_mi355x_set_max_workgroups": (None, [u]),
+        "liquid_mi355x_get_max_workgroups": (u, []),
+        "liquid_mi355x_firdecim_route": (i, [i, u, u, i, ull]),
+        "liquid_mi355x_firdecim_tile": (u, [i]),
+        "liquid_mi355x_firdecim_grid_cap": (u, [i, u, u, i]),
         "kaiser": (f, [u, u, f, f]),
         "hann": (f, [u, u]),
         "blackmanharris": (f, [u, u]),

@@ -25,6 +25,14 @@ checked; every output must be finite.
 Shared by tests/test_fir_bound.py (the oracle meets the bound: it is
 reachable, and the checker is pinned) and tests/test_gpu_fir_bound.py (every
 kernel, however the caller cuts the stream).
+
+The decimator (decim_reference, decim_case) is held to the same bound with
+the same checker: firdecim forms y[o] = sum_k h[k] x[oM - k] as one float32
+dot product (firdecim.c:195-204), there is no output scale, and its kernels
+are plain float32 multiply-adds in some order -- no split terms -- so
+gamma_T A with the sqrt(2) of a complex output is all there is, and
+(T + 8) 2^-23 A[o] holds it with A[o] = sum_k |h[k]| |x[oM - k]|.  Its
+envelopes put their edges on the kernels' tile seams (tests/test_gpu_persistent.py).
 """
 import functools
 import zlib
@@ -119,6 +127,14 @@ def case(t, hlen, name):
     return Case(t, hlen, name, h, x, scale_of(t))
 
 
+@functools.lru_cache(maxsize=None)
+def long_case(t, hlen, name, n):
+    """The envelope of case() repeated to n samples (np.resize), for streams
+    long enough to make a capped grid walk (tests/test_gpu_persistent.py)."""
+    h, x = signal(t, hlen, "%s x%d" % (name, n), np.resize(envelope(name, hlen), n))
+    return Case(t, hlen, name, h, x, scale_of(t))
+
+
 def carried_split(hlen):
     """Case (c): the length of the first call, which ends inside a level-1
     burst; the second call (at least 8192 samples) is all at 1e-5."""
@@ -144,6 +160,75 @@ def overflow_case(small):
     h = np.full(129, 2.0 ** e_h, np.float32)
     x = np.full(9000, 2.0 ** e_x + 0j, np.complex64)
     return Case("crcf", 129, "small" if small else "overflow", h, x, 1.0)
+
+
+# ------------------------------------------------------------------ firdecim
+def decim_reference(t, h, x, M):
+    """(y64, A) of the len(x) // M outputs of a decimator with zero initial
+    history: y64[o] = sum_k h[k] x[oM - k], A[o] = sum_k |h[k]| |x[oM - k]|, in
+    float64 / complex128.  One pass per tap over the input split by phase
+    (x[oM - k] with k = qM + r is phase (M - r) % M, row o - q - (r > 0)), so
+    every pass is a contiguous multiply-add over the outputs."""
+    nout = len(x) // M
+    wide = np.float64 if t == "rrrf" else np.complex128
+    hw = h.astype(np.complex128 if t == "cccf" else np.float64)
+    ah = np.abs(hw)
+    P = np.ascontiguousarray(x[:nout * M].astype(wide).reshape(nout, M).T)   # P[r, j] = x[jM + r]
+    aP = np.abs(P)
+    y64, A = np.zeros(nout, wide), np.zeros(nout)
+    for k in range(len(hw)):
+        q, r = divmod(k, M)
+        ph, d = (0, q) if r == 0 else (M - r, q + 1)
+        if d < nout:
+            y64[d:] += hw[k] * P[ph, :nout - d]
+            A[d:] += ah[k] * aP[ph, :nout - d]
+    return y64, A
+
+
+def decim_envelope(name, M, nout, cut):
+    """burst (1e-5 between the bursts) or gaps (exact zeros) over nout M input
+    samples, the edges of the bursts on the seams of the decimator's tiles:
+    256 and 512 outputs, that is multiples of a = 256 M and b = 512 M input
+    samples, and one sample either side; one burst ends with the last input
+    of the first `cut` outputs, so a call that starts at output `cut` sees it
+    only through the carried history; one runs to the end of the stream."""
+    assert name in ("burst", "gaps")
+    n, a, b = nout * M, 256 * M, 512 * M
+    assert nout >= 3 * 512 + 1 and 512 < cut < nout - 512
+    e = np.full(n, 1e-5 if name == "burst" else 0.0)
+    mid = max(2, nout // 512 // 2) * b   # a seam of both tile sizes far from the start
+    for lo, hi in ((0, 40), (a - 50, a + 1), (b - 1, b + 60), (3 * a + 1, 3 * a + 300), (2 * b - 200, 2 * b - 1),
+                   (5 * a, 5 * a + 1), (mid - 1, mid + 1), (cut * M - 300, cut * M),
+                   (n - 3 * M - 1, n)):
+        e[max(lo, 0):min(hi, n)] = 1.0
+    return e
+
+
+# (M, taps): one row per kernel the decimator's dispatch reaches for 16-byte
+# aligned or for unaligned input (tests/test_gpu_persistent.py names them),
+# each run for rrrf, crcf and cccf; DECIM_PLAIN is the one shape family that
+# reaches the undivided-taps kernel (about 6000 taps per unit of M and more)
+DECIM_ROWS = [(2, 80), (4, 37), (8, 128), (12, 96), (16, 128), (32, 256), (200, 801)]
+DECIM_PLAIN = ("rrrf", 2, 40000)
+DECIM_SMALL = (3 * 512 + 77, 700)   # (outputs, cut) of the small versions the oracle runs
+
+
+class DecimCase:
+    def __init__(self, t, M, hlen, name, nout, cut):
+        self.t, self.M, self.hlen, self.name, self.nout, self.cut = t, M, hlen, name, nout, cut
+        self.h, self.x = signal(t, hlen, "decim %d %s" % (M, name), decim_envelope(name, M, nout, cut))
+        self.y64, self.A = decim_reference(t, self.h, self.x, M)
+        for a in (self.x, self.y64, self.A):
+            a.setflags(write=False)
+
+    def check(self, y):
+        return check(self.t, self.hlen, y, self.y64, self.A)
+
+
+def decim_case(t, M, hlen, name, nout, cut):
+    """Not cached: a large-M case is a few hundred megabytes; its one test
+    runs every cut of the stream against it."""
+    return DecimCase(t, M, hlen, name, nout, cut)
 
 
 def report(t, hlen, y, y64, A):
