@@ -18,7 +18,9 @@
  * their output is written.
  *
  * There is no CPU fallback: without a usable HIP device every constructor
- * prints an error and exits (same failure style as the reference).
+ * prints an error and exits (same failure style as the reference).  The one
+ * exception is nco_crcf, whose per-sample interface is host arithmetic: it
+ * needs the device only from its first block call on.
  */
 #ifndef LIQUID_MI355X_H
 #define LIQUID_MI355X_H
@@ -751,6 +753,68 @@ void firpfbch2_crcf_execute_block_dev(firpfbch2_crcf _q, const liquid_float_comp
 void firpfbch2_crcf_set_stream(firpfbch2_crcf _q, void *_hip_stream);
 void *firpfbch2_crcf_get_stream(firpfbch2_crcf _q);
 void firpfbch2_crcf_synchronize(firpfbch2_crcf _q);
+
+/* ------------------------------------------------------------------------ */
+/* nco (liquid.h:5919-5999): crcf                                            */
+/* ------------------------------------------------------------------------ */
+/* Oscillator with PLL and mixer.  The per-sample interface runs on the host
+   and is the reference's arithmetic bit for bit (float32 phase, one wrap per
+   step, LIQUID_NCO: 256-entry sine table, LIQUID_VCO: sinf / cosf); create
+   needs no device.  mix_block_up / mix_block_down run on the GPU
+   (csrc/k_nco.hip): the phase of every sample is replayed bit for bit from a
+   host-built plan of checkpoints (host/nco_plan.c), so the phase after a block
+   equals the reference's and get_phase does not wait for the device.
+   LIQUID_NCO block outputs equal the reference's bit for bit where finite;
+   LIQUID_VCO ones use the device's sinf / cosf of the same phase.  In-place
+   (_y == _x) is allowed; otherwise the arrays must not overlap.  An object
+   with |frequency| > 2 pi, or a phase beyond 2 pi or not finite, runs block
+   calls in the host loop (device_eligible() == 0). */
+typedef enum { LIQUID_NCO = 0, LIQUID_VCO } liquid_ncotype;
+typedef struct nco_crcf_s *nco_crcf;
+nco_crcf nco_crcf_create(liquid_ncotype _type);
+void nco_crcf_destroy(nco_crcf _q);
+void nco_crcf_print(nco_crcf _q);
+void nco_crcf_reset(nco_crcf _q);
+float nco_crcf_get_frequency(nco_crcf _q);
+void nco_crcf_set_frequency(nco_crcf _q, float _f);
+void nco_crcf_adjust_frequency(nco_crcf _q, float _df);
+float nco_crcf_get_phase(nco_crcf _q);
+void nco_crcf_set_phase(nco_crcf _q, float _phi);
+void nco_crcf_adjust_phase(nco_crcf _q, float _dphi);
+void nco_crcf_step(nco_crcf _q);
+float nco_crcf_sin(nco_crcf _q);
+float nco_crcf_cos(nco_crcf _q);
+void nco_crcf_sincos(nco_crcf _q, float *_s, float *_c);
+void nco_crcf_cexpf(nco_crcf _q, liquid_float_complex *_y);
+void nco_crcf_pll_set_bandwidth(nco_crcf _q, float _bandwidth);
+void nco_crcf_pll_step(nco_crcf _q, float _dphi);
+void nco_crcf_mix_up(nco_crcf _q, liquid_float_complex _x, liquid_float_complex *_y);
+void nco_crcf_mix_down(nco_crcf _q, liquid_float_complex _x, liquid_float_complex *_y);
+void nco_crcf_mix_block_up(nco_crcf _q, liquid_float_complex *_x, liquid_float_complex *_y, unsigned int _N);
+void nco_crcf_mix_block_down(nco_crcf _q, liquid_float_complex *_x, liquid_float_complex *_y, unsigned int _N);
+/* liquid.h:5995-5999 */
+void liquid_unwrap_phase(float *_theta, unsigned int _n);
+void liquid_unwrap_phase2(float *_theta, unsigned int _n);
+/* extensions: device pointers (stream-ordered, no wait), stream control, the
+ * kernel's tile (samples per workgroup) and the plan's checkpoint spacing */
+void nco_crcf_mix_block_up_dev(nco_crcf _q, const liquid_float_complex *_dx, liquid_float_complex *_dy,
+                               unsigned long long _n);
+void nco_crcf_mix_block_down_dev(nco_crcf _q, const liquid_float_complex *_dx, liquid_float_complex *_dy,
+                                 unsigned long long _n);
+int nco_crcf_device_eligible(nco_crcf _q);
+void nco_crcf_set_stream(nco_crcf _q, void *_hip_stream);
+void nco_crcf_synchronize(nco_crcf _q);
+unsigned int liquid_mi355x_nco_tile(void);
+unsigned int liquid_mi355x_nco_checkpoint(void);
+/* The phases (and, LIQUID_NCO, table indices) a plan serves for positions
+ * 0 .. _n-1 from (_theta0, _d_theta), with its pre-period and period (0, 0 for
+ * the direct form); _theta / _index / _pre / _period may be NULL.  Returns _n,
+ * or -1 when the orbit has no period within the search limit.  No GPU call.
+ * The environment variable LQ_NCO_PLAN=direct or =periodic, read at create,
+ * makes an object build only that form (for tests). */
+long long liquid_mi355x_nco_walk(liquid_ncotype _type, float _theta0, float _d_theta, unsigned long long _n,
+                                 int _periodic, float *_theta, unsigned int *_index, unsigned long long *_pre,
+                                 unsigned long long *_period);
 
 /* ------------------------------------------------------------------------ */
 /* runtime extensions                                                        */

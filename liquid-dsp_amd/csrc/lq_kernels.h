@@ -414,6 +414,30 @@ void lqk_autocorr(int cx, unsigned int W, unsigned long long d, const void *hist
 void lqk_autocorr_single(int cx, unsigned int W, unsigned long long d, const void *hist, float *out,
                          unsigned *flag, unsigned seq, void *stream);
 
+/* ---------------------------------------------------------------- nco (k_nco.hip)
+ * y[i] = x[i] (cos th_i +- j sin th_i), i < n <= LQK_NCO_MAXN, th_i the
+ * oscillator's float32 phase before sample i, replayed from a phase plan
+ * (host/nco_plan.c): tab[c] = the phase before plan position c * LQK_NCO_CK;
+ * any other position is the checkpoint before it stepped forward (th += d_theta
+ * in float32, one wrap by 2 pi computed in double) fewer than LQK_NCO_CK times.
+ * Sample i stands at plan position p0 + i; with P > 0 positions >= pre repeat
+ * with period P (position g means pre + (g - pre) % P; p0 < pre + P; th_pre =
+ * the phase at pre) and tab covers [0, pre + P); with P == 0 tab covers
+ * [0, p0 + n).  vco == 0: sin th = sintab[k], cos th = sintab[(k + 64) & 255],
+ * k the reference's table index of th (sintab: 256 floats in device memory);
+ * vco != 0: sinf / cosf of th.  down: the conjugate rotator.  x == y allowed;
+ * otherwise they must not overlap.  LQK_NCO_TILE: samples per workgroup. */
+#define LQK_NCO_CK 64
+#define LQK_NCO_TILE 2048
+#define LQK_NCO_MAXN (1ull << 30)
+typedef struct {
+    const float *tab;
+    unsigned long long p0, pre, P;
+    float d_theta, th_pre;
+} lqk_nco_plan;
+void lqk_nco_mix(int vco, int down, const lqk_nco_plan *pl, const float *sintab, const void *x, void *y,
+                 unsigned long long n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -335,6 +335,55 @@ void lq_rs_block_dev_hb(lq_rs *q, const void *dx, unsigned long long nx, void *d
                         const lq_rs_hb *hb);
 lq_ctx *lq_rs_ctx(lq_rs *q);
 
+/* ---- the oscillator's phase plan (host/nco_plan.c): float32 phase
+ * arithmetic only -- no runtime call, no kernel launch, libc and libm alone */
+#define NCO_PI 3.14159265358979323846
+
+/* one step of nco.c:134-138 + 355-361: a float32 add, comparisons against the
+ * double pi, one wrap by 2 pi computed in double and rounded once */
+static inline float nco_step_theta(float th, float d)
+{
+    th += d;
+    if (th > NCO_PI) th -= 2 * NCO_PI;
+    else if (th < -NCO_PI) th += 2 * NCO_PI;
+    return th;
+}
+
+/* the sine table's index of a phase (nco.c:372): three separately rounded
+ * float32 operations (the library is compiled with -ffp-contract=off) */
+static inline unsigned int nco_table_index(float th)
+{
+    return ((unsigned int)(th * 40.743665f + 512.0f + 0.5f)) & 0xff;
+}
+
+static inline int nco_same_bits(float a, float b) { return memcmp(&a, &b, 4) == 0; }
+
+/* A plan belongs to one orbit: the phases theta0, step(theta0), ... at
+ * positions 0, 1, ...; tab[c] = the phase at position c * LQK_NCO_CK.  A
+ * direct plan covers positions 0 .. end; a periodic one every position:
+ * positions >= pre repeat every P (the phase at g is the phase at
+ * pre + (g - pre) % P), tab covers [0, pre + P) and th_pre is the phase at pre. */
+typedef struct {
+    float theta0, d_theta;
+    int valid, periodic;
+    float *tab;
+    size_t ntab, cap;
+    unsigned long long pre, P, end;
+    float th_pre;
+} nco_plan;
+
+void nco_plan_init(nco_plan *pl);
+void nco_plan_free(nco_plan *pl);
+/* the next n positions from theta0; 1, or 0 when out of memory (nothing is left allocated) */
+int nco_plan_build_direct(nco_plan *pl, float theta0, float d_theta, unsigned long long n);
+/* pre-period and period by cycle detection; 0 when pre + P would exceed cap
+ * positions (nothing is left allocated) */
+int nco_plan_build_periodic(nco_plan *pl, float theta0, float d_theta, unsigned long long cap);
+/* the table position that serves position g (g itself below pre + P) */
+unsigned long long nco_plan_reduce(const nco_plan *pl, unsigned long long g);
+/* the phase at position g: the checkpoint before it stepped forward */
+float nco_plan_at(const nco_plan *pl, unsigned long long g);
+
 /* generic dotprod engine */
 typedef struct lq_dotprod_s lq_dotprod;
 lq_dotprod *lq_dotprod_create(int kind, const float *h, unsigned int n);

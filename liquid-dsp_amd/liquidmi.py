@@ -379,6 +379,39 @@ def _declare(L):
         "liquid_mi355x_autocorr_tile": (u, []),
         "liquid_mi355x_autocorr_max_window": (u, []),
     })
+    sig.update({
+        "nco_crcf_create": (vp, [i]),
+        "nco_crcf_destroy": (None, [vp]),
+        "nco_crcf_print": (None, [vp]),
+        "nco_crcf_reset": (None, [vp]),
+        "nco_crcf_get_frequency": (f, [vp]),
+        "nco_crcf_set_frequency": (None, [vp, f]),
+        "nco_crcf_adjust_frequency": (None, [vp, f]),
+        "nco_crcf_get_phase": (f, [vp]),
+        "nco_crcf_set_phase": (None, [vp, f]),
+        "nco_crcf_adjust_phase": (None, [vp, f]),
+        "nco_crcf_step": (None, [vp]),
+        "nco_crcf_sin": (f, [vp]),
+        "nco_crcf_cos": (f, [vp]),
+        "nco_crcf_sincos": (None, [vp, vp, vp]),
+        "nco_crcf_cexpf": (None, [vp, vp]),
+        "nco_crcf_pll_set_bandwidth": (None, [vp, f]),
+        "nco_crcf_pll_step": (None, [vp, f]),
+        "nco_crcf_mix_up": (None, [vp, cfloat, vp]),
+        "nco_crcf_mix_down": (None, [vp, cfloat, vp]),
+        "nco_crcf_mix_block_up": (None, [vp, vp, vp, u]),
+        "nco_crcf_mix_block_down": (None, [vp, vp, vp, u]),
+        "nco_crcf_mix_block_up_dev": (None, [vp, vp, vp, ull]),
+        "nco_crcf_mix_block_down_dev": (None, [vp, vp, vp, ull]),
+        "nco_crcf_device_eligible": (i, [vp]),
+        "nco_crcf_set_stream": (None, [vp, vp]),
+        "nco_crcf_synchronize": (None, [vp]),
+        "liquid_unwrap_phase": (None, [vp, u]),
+        "liquid_unwrap_phase2": (None, [vp, u]),
+        "liquid_mi355x_nco_tile": (u, []),
+        "liquid_mi355x_nco_checkpoint": (u, []),
+        "liquid_mi355x_nco_walk": (C.c_longlong, [i, f, f, ull, i, vp, vp, vp, vp]),
+    })
     for d in FIRDES_DESIGNS:
         sig["liquid_firdes_" + d] = (None, [u, u, f, f, vp])
     sig.update({
@@ -1173,6 +1206,139 @@ class AutoCorr(_Obj):
 
     def get_energy(self):
         return float(self._fn("_get_energy")(self.q))
+
+
+LIQUID_NCO, LIQUID_VCO = 0, 1
+
+
+class NCO(_Obj):
+    """nco_crcf: oscillator, PLL and mixer; typ LIQUID_NCO (sine table) or
+    LIQUID_VCO (sinf / cosf).  The per-sample calls run on the host (the
+    constructor needs no GPU); mix_block_up / mix_block_down run on the GPU when
+    device_eligible, else in the library's host loop.  plan="direct" or
+    "periodic" forces the form of the phase plan (LQ_NCO_PLAN, for tests)."""
+    prefix = "nco_crcf"
+    TILE = _LibConst("liquid_mi355x_nco_tile")               # samples per workgroup
+    CHECKPOINT = _LibConst("liquid_mi355x_nco_checkpoint")   # positions per checkpoint of the plan
+
+    def __init__(self, typ=LIQUID_NCO, plan=None):
+        assert typ in (LIQUID_NCO, LIQUID_VCO) and plan in (None, "direct", "periodic")
+        self.type = typ
+        old = os.environ.get("LQ_NCO_PLAN")
+        try:
+            os.environ.pop("LQ_NCO_PLAN", None)
+            if plan:
+                os.environ["LQ_NCO_PLAN"] = plan
+            self.q = self._fn("_create")(typ)
+        finally:
+            os.environ.pop("LQ_NCO_PLAN", None)
+            if old is not None:
+                os.environ["LQ_NCO_PLAN"] = old
+
+    @property
+    def device_eligible(self):
+        return bool(self._fn("_device_eligible")(self.q))
+
+    def reset(self):
+        self._fn("_reset")(self.q)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
+
+    def get_frequency(self):
+        return np.float32(self._fn("_get_frequency")(self.q))
+
+    def set_frequency(self, v):
+        self._fn("_set_frequency")(self.q, float(v))
+
+    def adjust_frequency(self, v):
+        self._fn("_adjust_frequency")(self.q, float(v))
+
+    def get_phase(self):
+        return np.float32(self._fn("_get_phase")(self.q))
+
+    def set_phase(self, v):
+        self._fn("_set_phase")(self.q, float(v))
+
+    def adjust_phase(self, v):
+        self._fn("_adjust_phase")(self.q, float(v))
+
+    def step(self):
+        self._fn("_step")(self.q)
+
+    def sin(self):
+        return np.float32(self._fn("_sin")(self.q))
+
+    def cos(self):
+        return np.float32(self._fn("_cos")(self.q))
+
+    def sincos(self):
+        s, c = C.c_float(), C.c_float()
+        self._fn("_sincos")(self.q, C.byref(s), C.byref(c))
+        return np.float32(s.value), np.float32(c.value)
+
+    def cexpf(self):
+        y = np.zeros(1, np.complex64)
+        self._fn("_cexpf")(self.q, ptr(y))
+        return y[0]
+
+    def pll_set_bandwidth(self, bw):
+        self._fn("_pll_set_bandwidth")(self.q, float(bw))
+
+    def pll_step(self, dphi):
+        self._fn("_pll_step")(self.q, float(dphi))
+
+    def mix_up(self, v):
+        y = np.zeros(1, np.complex64)
+        self._fn("_mix_up")(self.q, _by_value(v, CRCF), ptr(y))
+        return y[0]
+
+    def mix_down(self, v):
+        y = np.zeros(1, np.complex64)
+        self._fn("_mix_down")(self.q, _by_value(v, CRCF), ptr(y))
+        return y[0]
+
+    def _block(self, name, x, n, y, inplace):
+        if isinstance(x, DeviceBuffer):
+            n = x.nbytes // 8 if n is None else n
+            self._fn(name + "_dev")(self.q, x.p, (x if y is None else y).p, n)
+            return x if y is None else y
+        x = _samples(x, CRCF)
+        y = x.copy() if inplace else np.zeros(len(x), np.complex64)
+        self._fn(name)(self.q, ptr(y) if inplace else ptr(x), ptr(y), len(x))
+        return y
+
+    def mix_block_up(self, x, n=None, y=None, inplace=False):
+        """y = x exp(+j theta), stepping.  x a numpy array (returns the output
+        array; inplace: the library writes over its input array) or a
+        DeviceBuffer (n samples, default all of it, into DeviceBuffer y,
+        default x itself; stream-ordered: synchronize() before reading)."""
+        return self._block("_mix_block_up", x, n, y, inplace)
+
+    def mix_block_down(self, x, n=None, y=None, inplace=False):
+        return self._block("_mix_block_down", x, n, y, inplace)
+
+    def mix_block_up_dev(self, dx, dy, n):
+        self._fn("_mix_block_up_dev")(self.q, dx, dy, n)
+
+    def mix_block_down_dev(self, dx, dy, n):
+        self._fn("_mix_block_down_dev")(self.q, dx, dy, n)
+
+
+def nco_walk(typ, theta0, d_theta, n, periodic):
+    """liquid_mi355x_nco_walk: (theta, index, pre-period, period) of the plan
+    from (theta0, d_theta) for positions 0 .. n-1, or None if there is no plan."""
+    th, idx = np.zeros(n, np.float32), np.zeros(n, np.uint32)
+    pre, per = ull(0), ull(0)
+    r = lib().liquid_mi355x_nco_walk(typ, float(theta0), float(d_theta), n, 1 if periodic else 0, ptr(th), ptr(idx),
+                                     C.byref(pre), C.byref(per))
+    return None if r < 0 else (th, idx, pre.value, per.value)
+
+
+def unwrap_phase(theta, advanced=False):
+    t = np.array(theta, np.float32)
+    (lib().liquid_unwrap_phase2 if advanced else lib().liquid_unwrap_phase)(ptr(t), len(t))
+    return t
 
 
 IIRDES_FILTERTYPES = {"butter": 0, "cheby1": 1, "cheby2": 2, "ellip": 3, "bessel": 4}
