@@ -18,9 +18,9 @@
  * their output is written.
  *
  * There is no CPU fallback: without a usable HIP device every constructor
- * prints an error and exits (same failure style as the reference).  The one
- * exception is nco_crcf, whose per-sample interface is host arithmetic: it
- * needs the device only from its first block call on.
+ * prints an error and exits (same failure style as the reference).  The
+ * exceptions are nco_crcf, freqmod and freqdem, whose per-sample interface is
+ * host arithmetic: they need the device only from their first block call on.
  */
 #ifndef LIQUID_MI355X_H
 #define LIQUID_MI355X_H
@@ -815,6 +815,62 @@ unsigned int liquid_mi355x_nco_checkpoint(void);
 long long liquid_mi355x_nco_walk(liquid_ncotype _type, float _theta0, float _d_theta, unsigned long long _n,
                                  int _periodic, float *_theta, unsigned int *_index, unsigned long long *_pre,
                                  unsigned long long *_period);
+
+/* ------------------------------------------------------------------------ */
+/* freqmod (liquid.h:5329-5372), freqdem (liquid.h:5548-5591)                */
+/* ------------------------------------------------------------------------ */
+/* Analog FM modulator and demodulator.  As with nco, the per-sample calls run
+   on the host and are the reference's arithmetic, and create needs no device;
+   the block calls run on the GPU (csrc/k_freqmodem.hip).
+   freqmod: a phase accumulator modulo 2^16, advanced by (int)roundf(kf 2^16 m),
+   indexes a 1024-entry table; the block call is a prefix sum over the integer
+   increments, so outputs and accumulator equal the per-sample loop's bit for
+   bit.  A product that is not finite or reaches 2^31 in magnitude adds 0.
+   freqdem: m[n] = arg(conj(r[n-1]) r[n]) / (2 pi kf); block outputs are within
+   5 2^-23 (relative) of that argument taken exactly of the float32 product. */
+typedef struct freqmod_s *freqmod;
+freqmod freqmod_create(float _kf);
+void freqmod_destroy(freqmod _q);
+void freqmod_print(freqmod _q);
+void freqmod_reset(freqmod _q);
+void freqmod_modulate(freqmod _q, float _m, liquid_float_complex *_s);
+void freqmod_modulate_block(freqmod _q, float *_m, unsigned int _n, liquid_float_complex *_s);
+typedef struct freqdem_s *freqdem;
+freqdem freqdem_create(float _kf);
+void freqdem_destroy(freqdem _q);
+void freqdem_print(freqdem _q);
+void freqdem_reset(freqdem _q);
+void freqdem_demodulate(freqdem _q, liquid_float_complex _r, float *_m);
+void freqdem_demodulate_block(freqdem _q, liquid_float_complex *_r, unsigned int _n, float *_m);
+/* extensions.  Device pointers: stream-ordered, no wait; input and output must
+ * not overlap (their element sizes differ).  freqmod_get_phase: the
+ * accumulator (after a device call it waits for it); freqmod_get_table: the
+ * 1024 table entries.
+ * freqdem_create_channels: the lag-_M discriminator m[n] = arg(conj(r[n-_M])
+ * r[n]) / (2 pi kf), state the last _M samples (zero after create and reset):
+ * fed a channelizer's frame-major output it demodulates every channel, in the
+ * same layout.  freqdem_create(kf) is _M = 1; every call works on either, a
+ * block need not be a multiple of _M and may be shorter than _M.
+ * Tiles (samples per workgroup); freqmod_scan_pass: the tiles one pass of the
+ * scan across tile sums covers (the one carry boundary above the tile);
+ * freqdem_switch: the _M from which a lane walks the frames of its own
+ * channel instead of reading its neighbour from a staged tile;
+ * freqdem_frames: the frames of one such walk. */
+void freqmod_modulate_block_dev(freqmod _q, const float *_dm, unsigned long long _n, liquid_float_complex *_ds);
+unsigned int freqmod_get_phase(freqmod _q);
+void freqmod_get_table(freqmod _q, liquid_float_complex *_tab);
+void freqmod_set_stream(freqmod _q, void *_hip_stream);
+void freqmod_synchronize(freqmod _q);
+freqdem freqdem_create_channels(float _kf, unsigned int _M);
+unsigned int freqdem_get_channels(freqdem _q);
+void freqdem_demodulate_block_dev(freqdem _q, const liquid_float_complex *_dr, unsigned long long _n, float *_dm);
+void freqdem_set_stream(freqdem _q, void *_hip_stream);
+void freqdem_synchronize(freqdem _q);
+unsigned int liquid_mi355x_freqmod_tile(void);
+unsigned int liquid_mi355x_freqmod_scan_pass(void);
+unsigned int liquid_mi355x_freqdem_tile(void);
+unsigned int liquid_mi355x_freqdem_switch(void);
+unsigned int liquid_mi355x_freqdem_frames(void);
 
 /* ------------------------------------------------------------------------ */
 /* runtime extensions                                                        */

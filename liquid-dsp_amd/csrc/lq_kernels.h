@@ -438,6 +438,31 @@ typedef struct {
 void lqk_nco_mix(int vco, int down, const lqk_nco_plan *pl, const float *sintab, const void *x, void *y,
                  unsigned long long n, void *stream);
 
+/* ---------------------------------------------------------------- freqmod / freqdem (k_freqmodem.hip)
+ * freqmod: phase_i = acc_in[0] + sum_{k <= i} inc(m[k]) modulo 2^16, inc(m) =
+ * (int)roundf(ref * m) reduced modulo 2^16 (0 where the product is not finite
+ * or reaches 2^31 in magnitude); s[i] = tab[((phase_i + 0x20) >> 6) & 0x3ff],
+ * tab 1024 complex values in device memory, 16-byte aligned; acc_out[0] =
+ * phase_{n-1}.  n <= LQK_FREQMOD_MAXN; sums: ceil(n / LQK_FREQMOD_TILE) words of
+ * scratch; m and s must not overlap.  LQK_FREQMOD_TILE: samples per workgroup;
+ * LQK_FREQMOD_PASS: tile sums per pass of the one-workgroup scan across tiles.
+ * freqdem: m[i] = arg(conj(p_i) r[i]) * ref, p_i = r[i - M] or, for i < M,
+ * hist[i] (hist: the M samples before the call, oldest first); hist_out: the
+ * last M samples of hist ++ r (not hist itself).  M < LQK_FREQDEM_SWITCH: a
+ * tile of LQK_FREQDEM_TILE samples per workgroup with the halo in LDS; else a
+ * lane walks LQK_FREQDEM_FRAMES frames of its own channel. */
+#define LQK_FREQMOD_TILE 2048
+#define LQK_FREQMOD_PASS 1024
+#define LQK_FREQMOD_MAXN (1ull << 30)
+#define LQK_FREQDEM_TILE 2048
+#define LQK_FREQDEM_SWITCH 128
+#define LQK_FREQDEM_FRAMES 16
+#define LQK_FREQDEM_MAXN (1ull << 30)
+void lqk_freqmod(float ref, const void *tab, const unsigned *acc_in, unsigned *acc_out, unsigned *sums,
+                 const float *m, void *s, unsigned long long n, void *stream);
+void lqk_freqdem(float ref, unsigned M, const void *hist, void *hist_out, const void *r, float *m,
+                 unsigned long long n, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -411,6 +411,33 @@ def _declare(L):
         "liquid_mi355x_nco_tile": (u, []),
         "liquid_mi355x_nco_checkpoint": (u, []),
         "liquid_mi355x_nco_walk": (C.c_longlong, [i, f, f, ull, i, vp, vp, vp, vp]),
+        "freqmod_create": (vp, [f]),
+        "freqmod_destroy": (None, [vp]),
+        "freqmod_print": (None, [vp]),
+        "freqmod_reset": (None, [vp]),
+        "freqmod_modulate": (None, [vp, f, vp]),
+        "freqmod_modulate_block": (None, [vp, vp, u, vp]),
+        "freqmod_modulate_block_dev": (None, [vp, vp, ull, vp]),
+        "freqmod_get_phase": (u, [vp]),
+        "freqmod_get_table": (None, [vp, vp]),
+        "freqmod_set_stream": (None, [vp, vp]),
+        "freqmod_synchronize": (None, [vp]),
+        "freqdem_create": (vp, [f]),
+        "freqdem_create_channels": (vp, [f, u]),
+        "freqdem_get_channels": (u, [vp]),
+        "freqdem_destroy": (None, [vp]),
+        "freqdem_print": (None, [vp]),
+        "freqdem_reset": (None, [vp]),
+        "freqdem_demodulate": (None, [vp, cfloat, vp]),
+        "freqdem_demodulate_block": (None, [vp, vp, u, vp]),
+        "freqdem_demodulate_block_dev": (None, [vp, vp, ull, vp]),
+        "freqdem_set_stream": (None, [vp, vp]),
+        "freqdem_synchronize": (None, [vp]),
+        "liquid_mi355x_freqmod_tile": (u, []),
+        "liquid_mi355x_freqmod_scan_pass": (u, []),
+        "liquid_mi355x_freqdem_tile": (u, []),
+        "liquid_mi355x_freqdem_switch": (u, []),
+        "liquid_mi355x_freqdem_frames": (u, []),
     })
     for d in FIRDES_DESIGNS:
         sig["liquid_firdes_" + d] = (None, [u, u, f, f, vp])
@@ -1339,6 +1366,100 @@ def unwrap_phase(theta, advanced=False):
     t = np.array(theta, np.float32)
     (lib().liquid_unwrap_phase2 if advanced else lib().liquid_unwrap_phase)(ptr(t), len(t))
     return t
+
+
+class FreqMod(_Obj):
+    """freqmod: analog FM modulator, s[n] = table[phase >> 6], phase the sum of
+    roundf(kf 2^16 m[k]) modulo 2^16.  modulate() runs on the host (the
+    constructor needs no GPU); modulate_block runs on the GPU."""
+    prefix = "freqmod"
+    TILE = _LibConst("liquid_mi355x_freqmod_tile")            # samples per workgroup
+    SCAN_PASS = _LibConst("liquid_mi355x_freqmod_scan_pass")  # tiles per pass of the scan across tile sums
+
+    def __init__(self, kf):
+        self.kf = float(kf)
+        self.q = self._fn("_create")(self.kf)
+
+    def reset(self):
+        self._fn("_reset")(self.q)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
+
+    def get_phase(self):
+        return int(self._fn("_get_phase")(self.q))
+
+    def get_table(self):
+        t = np.zeros(1024, np.complex64)
+        self._fn("_get_table")(self.q, ptr(t))
+        return t
+
+    def modulate(self, m):
+        s = np.zeros(1, np.complex64)
+        self._fn("_modulate")(self.q, float(m), ptr(s))
+        return s[0]
+
+    def modulate_block(self, m, n=None, s=None):
+        """m a numpy array (returns the output array) or a DeviceBuffer (n
+        samples, default all of it, into DeviceBuffer s; stream-ordered:
+        synchronize() before reading)"""
+        if isinstance(m, DeviceBuffer):
+            n = m.nbytes // 4 if n is None else n
+            self._fn("_modulate_block_dev")(self.q, m.p, n, s.p)
+            return s
+        m = np.ascontiguousarray(m, np.float32)
+        s = np.zeros(len(m), np.complex64)
+        self._fn("_modulate_block")(self.q, ptr(m), len(m), ptr(s))
+        return s
+
+    def modulate_block_dev(self, dm, n, ds):
+        self._fn("_modulate_block_dev")(self.q, dm, n, ds)
+
+
+class FreqDem(_Obj):
+    """freqdem: analog FM demodulator, m[n] = arg(conj(r[n-channels]) r[n]) /
+    (2 pi kf); channels > 1 demodulates interleaved channels (a channelizer's
+    frame-major output).  demodulate() runs on the host (the constructor needs
+    no GPU); demodulate_block runs on the GPU."""
+    prefix = "freqdem"
+    TILE = _LibConst("liquid_mi355x_freqdem_tile")       # samples per workgroup (channels < SWITCH)
+    SWITCH = _LibConst("liquid_mi355x_freqdem_switch")   # channels from which a lane walks its own channel
+    FRAMES = _LibConst("liquid_mi355x_freqdem_frames")   # frames of one such walk
+
+    def __init__(self, kf, channels=1):
+        self.kf, self.channels = float(kf), int(channels)
+        self.q = self._fn("_create")(self.kf) if self.channels == 1 else \
+            self._fn("_create_channels")(self.kf, self.channels)
+
+    def reset(self):
+        self._fn("_reset")(self.q)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
+
+    def get_channels(self):
+        return int(self._fn("_get_channels")(self.q))
+
+    def demodulate(self, r):
+        m = np.zeros(1, np.float32)
+        self._fn("_demodulate")(self.q, _by_value(r, CRCF), ptr(m))
+        return m[0]
+
+    def demodulate_block(self, r, n=None, m=None):
+        """r a numpy array (returns the output array) or a DeviceBuffer (n
+        samples, default all of it, into DeviceBuffer m; stream-ordered:
+        synchronize() before reading)"""
+        if isinstance(r, DeviceBuffer):
+            n = r.nbytes // 8 if n is None else n
+            self._fn("_demodulate_block_dev")(self.q, r.p, n, m.p)
+            return m
+        r = _samples(r, CRCF)
+        m = np.zeros(len(r), np.float32)
+        self._fn("_demodulate_block")(self.q, ptr(r), len(r), ptr(m))
+        return m
+
+    def demodulate_block_dev(self, dr, n, dm):
+        self._fn("_demodulate_block_dev")(self.q, dr, n, dm)
 
 
 IIRDES_FILTERTYPES = {"butter": 0, "cheby1": 1, "cheby2": 2, "ellip": 3, "bessel": 4}
