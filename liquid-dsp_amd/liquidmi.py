@@ -843,6 +843,15 @@ class FirPfbch(_Obj):
         self._fn("_execute_block")(self.q, ptr(x), nb, ptr(y))
         return y
 
+    def reset(self):
+        self._fn("_reset")(self.q)
+
+    def execute_block_dev(self, dx, nblocks, dy):
+        self._fn("_execute_block_dev")(self.q, dx, nblocks, dy)
+
+    def synchronize(self):
+        lib().liquid_mi355x_device_synchronize()
+
 
 class FirPfbch2(_Obj):
     prefix = "firpfbch2_crcf"
