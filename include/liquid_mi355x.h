@@ -915,6 +915,39 @@ int liquid_mi355x_firdecim_route(int _kind, unsigned int _M, unsigned int _h_len
                                  unsigned long long _nout);
 unsigned int liquid_mi355x_firdecim_tile(int _route);
 unsigned int liquid_mi355x_firdecim_grid_cap(int _kind, unsigned int _M, unsigned int _h_len, int _route);
+/* Which kernel the first block call of _nx inputs takes on a fresh resamp
+ * object (_kind as above; no GPU call), computed by the launch's own
+ * decision, and in *_tile (may be NULL) its tile: inputs per wave tile for
+ * the input-plan kernels (RESAMP3: tin; RESAMP: 2048 per workgroup; GENERIC:
+ * 256 per workgroup), outputs per wave tile (256) for the four rate classes
+ * of the output-plan kernel k_resamp4.  -1: bad arguments. */
+enum {
+    LIQUID_MI355X_RESAMP3_CONST = 0,   /* k_resamp3, constant pair-table stride (npfb <= 64) */
+    LIQUID_MI355X_RESAMP3_STRIDE = 1,  /* k_resamp3, run-time stride */
+    LIQUID_MI355X_RESAMP = 2,          /* k_resamp: 8 inputs per lane (r > ~52, or the table outside LDS) */
+    LIQUID_MI355X_RESAMP_GENERIC = 3,  /* k_resamp_generic: m > 16 */
+    LIQUID_MI355X_RESAMP4_UP = 4,      /* k_resamp4, 1 <= r <= 2 */
+    LIQUID_MI355X_RESAMP4_UP_R4 = 5,   /* k_resamp4, r > 2 */
+    LIQUID_MI355X_RESAMP4_DOWN = 6,    /* k_resamp4, 1/2 < r < 1 */
+    LIQUID_MI355X_RESAMP4_DOWN_DN = 7  /* k_resamp4, 1/4 < r <= 1/2 */
+};
+int liquid_mi355x_resamp_route(int _kind, float _rate, unsigned int _m, unsigned int _npfb, unsigned long long _nx,
+                               unsigned int *_tile);
+/* Which kernel a resamp2 block call of this mode (LQMI_RESAMP2_*), _m and _bytes of input
+ * takes, and in *_tile (may be NULL) the calls per workgroup tile.  -1: bad
+ * arguments. */
+enum {
+    LIQUID_MI355X_RESAMP2_K_FILTER = 0,  /* k_resamp2: filter mode, one call per lane */
+    LIQUID_MI355X_RESAMP2_K_TILED_B = 1, /* k_resamp2_tiled_b: m <= 16 */
+    LIQUID_MI355X_RESAMP2_K_TILED = 2    /* k_resamp2_tiled */
+};
+int liquid_mi355x_resamp2_route(int _mode, unsigned int _m, unsigned long long _bytes, unsigned int *_tile);
+/* The resampler kernel (LIQUID_MI355X_RESAMP*) of the first block call of _nx
+ * inputs on a fresh msresamp, its tile, and in *_hm (may be NULL) the
+ * semi-length of the half-band stage fused into that launch (0: none; the
+ * fused launch's tile is shorter by the stage's halo). */
+int liquid_mi355x_msresamp_route(int _kind, float _rate, float _As, unsigned long long _nx, unsigned int *_tile,
+                                 unsigned int *_hm);
 
 #ifdef __cplusplus
 }

@@ -358,12 +358,13 @@ constexpr int RS3_FIT = 15;      // a tile's fixed cost in evaluation passes x 1
 // table rows (float2 units) of k_resamp3
 template <int L>
 constexpr int rs3_rows() { return L + 1; }
-template <int L, typename S, int RSC>
-inline size_t rs3_lds_bytes(int npfb)
+// dynamic LDS of k_resamp3: the pair table at row stride rs, then per wave
+// the window of ssz-byte samples and the output descriptors
+inline size_t rs3_lds_bytes(int L, size_t ssz, int rs)
 {
-    constexpr int TS = W3_TIN + L + 2;
-    return (size_t)2 * rs3_rows<L>() * rs2_rs<RSC>(npfb) * sizeof(float2) +
-           (size_t)(NT3 / 64) * (((TS + 2) * sizeof(S) + 15) / 16 * 16 + (W3_CAP + 2) * 8);
+    const int TS = W3_TIN + L + 2;
+    return (size_t)2 * (L + 1) * rs * sizeof(float2) +
+           (size_t)(NT3 / 64) * (((TS + 2) * ssz + 15) / 16 * 16 + (W3_CAP + 2) * 8);
 }
 
 template <int L, typename S, int RSC>
@@ -556,15 +557,23 @@ __global__ __launch_bounds__(NT3, RS3_BLK) void k_resamp3(lqk_rs_plan pl, unsign
     }
 }
 
-template <int L, typename S>
-void launch_rs(const lqk_rs_plan &pl, unsigned long long g0, unsigned long long K0, int npfb, float del,
-               const float2 *taps, const float2 *taps2, const S *hist, const S *x, long long n, S *y,
-               unsigned long long nout, hipStream_t st)
+// Where a launch goes and its tile: the one decision behind lqk_resamp's
+// launches and lqk_resamp_route.  ssz: bytes per sample; P, pre, end: the plan's
+struct rs_route {
+    int route;     // LQK_RS_ROUTE_*
+    int tile;      // inputs per tile: tin of k_resamp3, RS_R NT of k_resamp, NT of k_resamp_generic
+    size_t lds;    // dynamic LDS of the launch
+};
+constexpr int RS3_RSC = 33;   // constant pair-table stride for npfb <= 64 (immediate tap offsets)
+
+rs_route rs_decide(size_t ssz, unsigned long long P, unsigned long long pre, unsigned long long end, int npfb,
+                   int L, float del, bool has_taps2)
 {
-    constexpr int RSC = 33;                    // constant pair-table stride for npfb <= 64 (immediate tap offsets)
-    const bool cst = npfb <= 2 * (RSC - 1);
-    const size_t lds3 = cst ? rs3_lds_bytes<L, S, RSC>(npfb) : rs3_lds_bytes<L, S, 0>(npfb);
-    if (taps2 != nullptr && lds3 <= 80 * 1024 && pl.P < (1ull << 31) && (pl.pre < (1ull << 62) || pl.end < (1ull << 62))) {
+    const bool lds_ok = (size_t)npfb * L * sizeof(float2) <= 64 * 1024;
+    if (!(lds_ok && L >= 2 && L <= 32 && (L % 2) == 0)) return rs_route{LQK_RS_ROUTE_GENERIC, NT, 0};
+    const bool cst = npfb <= 2 * (RS3_RSC - 1);
+    const size_t lds3 = rs3_lds_bytes(L, ssz, cst ? rs2_rs<RS3_RSC>(npfb) : rs2_rs<0>(npfb));
+    if (has_taps2 && lds3 <= 80 * 1024 && P < (1ull << 31) && (pre < (1ull << 62) || end < (1ull << 62))) {
         // inputs per wave tile (a multiple of 4): its outputs, at most
         // (tin + 2) r + 2 (tau moves by 1/r per output and by -1 per input
         // within [-1/npfb, 1 + 1/r)), fit the W3_CAP output slots
@@ -588,24 +597,35 @@ void launch_rs(const lqk_rs_plan &pl, unsigned long long g0, unsigned long long 
             }
             tin = bt;
         }
-        if (std::ceil((tin + 2) * r) + 2 <= W3_CAP) {   // else (r > ~52): the per-input kernel below
-            const long long ntiles = (n + tin - 1) / tin;
-            const long long wgs = (ntiles + NT3 / 64 - 1) / (NT3 / 64);
-            const int blk = lds3 <= 160 * 1024 / RS3_BLK ? RS3_BLK : (int)(160 * 1024 / lds3);
-            const unsigned nb = lqrt_grid((unsigned long long)wgs, 256u * (unsigned)blk);   // persistent: blk per CU
-            if (cst)
-                hipLaunchKernelGGL((k_resamp3<L, S, RSC>), dim3(nb), dim3(NT3), lds3, st, pl, g0, K0, npfb, del,
-                                   taps2, hist, x, n, y, (int)nout, tin);
-            else
-                hipLaunchKernelGGL((k_resamp3<L, S, 0>), dim3(nb), dim3(NT3), lds3, st, pl, g0, K0, npfb, del,
-                                   taps2, hist, x, n, y, (int)nout, tin);
-            return;
-        }
+        if (std::ceil((tin + 2) * r) + 2 <= W3_CAP)   // else (r > ~52): the per-input kernel below
+            return rs_route{cst ? LQK_RS_ROUTE_R3_CONST : LQK_RS_ROUTE_R3_STRIDE, tin, lds3};
+    }
+    return rs_route{LQK_RS_ROUTE_RS, RS_R * NT, (size_t)npfb * L * sizeof(float2)};
+}
+
+template <int L, typename S>
+void launch_rs(const rs_route &rt, const lqk_rs_plan &pl, unsigned long long g0, unsigned long long K0, int npfb,
+               float del, const float2 *taps, const float2 *taps2, const S *hist, const S *x, long long n, S *y,
+               unsigned long long nout, hipStream_t st)
+{
+    if (rt.route == LQK_RS_ROUTE_R3_CONST || rt.route == LQK_RS_ROUTE_R3_STRIDE) {
+        const size_t lds3 = rt.lds;
+        const int tin = rt.tile;
+        const long long ntiles = (n + tin - 1) / tin;
+        const long long wgs = (ntiles + NT3 / 64 - 1) / (NT3 / 64);
+        const int blk = lds3 <= 160 * 1024 / RS3_BLK ? RS3_BLK : (int)(160 * 1024 / lds3);
+        const unsigned nb = lqrt_grid((unsigned long long)wgs, 256u * (unsigned)blk);   // persistent: blk per CU
+        if (rt.route == LQK_RS_ROUTE_R3_CONST)
+            hipLaunchKernelGGL((k_resamp3<L, S, RS3_RSC>), dim3(nb), dim3(NT3), lds3, st, pl, g0, K0, npfb, del,
+                               taps2, hist, x, n, y, (int)nout, tin);
+        else
+            hipLaunchKernelGGL((k_resamp3<L, S, 0>), dim3(nb), dim3(NT3), lds3, st, pl, g0, K0, npfb, del,
+                               taps2, hist, x, n, y, (int)nout, tin);
+        return;
     }
     const long long lanes = (n + RS_R - 1) / RS_R;
     const unsigned nb = (unsigned)((lanes + NT - 1) / NT);
-    hipLaunchKernelGGL((k_resamp<L, S>), dim3(nb), dim3(NT), (size_t)npfb * L * sizeof(float2), st, pl, g0, K0,
-                       npfb, del, taps, hist, x, n, y);
+    hipLaunchKernelGGL((k_resamp<L, S>), dim3(nb), dim3(NT), rt.lds, st, pl, g0, K0, npfb, del, taps, hist, x, n, y);
 }
 
 template <typename S>
@@ -617,12 +637,12 @@ void run_rs(const lqk_rs_plan *pl, unsigned long long g0, unsigned long long K0,
     const S *hs = (const S *)hist, *xi = (const S *)x;
     S *yo = (S *)y;
     const long long nn = (long long)n;
-    const bool lds_ok = (size_t)npfb * L * sizeof(float2) <= 64 * 1024;
-#define LQ_RS_CASE(LL)                                                                                     \
-    case LL:                                                                                               \
-        launch_rs<LL, S>(*pl, g0, K0, (int)npfb, del, tp, (const float2 *)taps2, hs, xi, nn, yo, nout, st); \
+    const rs_route rt = rs_decide(sizeof(S), pl->P, pl->pre, pl->end, (int)npfb, (int)L, del, taps2 != nullptr);
+#define LQ_RS_CASE(LL)                                                                                         \
+    case LL:                                                                                                   \
+        launch_rs<LL, S>(rt, *pl, g0, K0, (int)npfb, del, tp, (const float2 *)taps2, hs, xi, nn, yo, nout, st); \
         return;
-    if (lds_ok && L <= 32 && (L % 2) == 0) {
+    if (rt.route != LQK_RS_ROUTE_GENERIC) {
         switch (L) {
             LQ_RS_CASE(2)
             LQ_RS_CASE(4)
@@ -649,6 +669,14 @@ void run_rs(const lqk_rs_plan *pl, unsigned long long g0, unsigned long long K0,
 }
 
 } // namespace
+
+extern "C" int lqk_resamp_route(int real_io, unsigned long long P, unsigned long long pre, unsigned long long end,
+                                unsigned int npfb, unsigned int L, float del, unsigned int *tile)
+{
+    const rs_route rt = rs_decide(real_io ? 4 : 8, P, pre, end, (int)npfb, (int)L, del, true);
+    if (tile) *tile = (unsigned int)rt.tile;
+    return rt.route;
+}
 
 extern "C" void lqk_resamp(int real_io, const lqk_rs_plan *pl, unsigned long long g0, unsigned long long K0,
                            unsigned int npfb, unsigned int L, float del, const void *taps, const void *taps2,

@@ -310,6 +310,14 @@ __global__ __launch_bounds__(NT) void k_resamp2_hist(R2Args a, long long push0, 
     (p ? out1 : out0)[kk] = v;
 }
 
+// The kernel a launch takes: the one decision behind run_r2 and
+// lqk_resamp2_route.  xbytes: the bytes of x the launch reads
+int r2_decide(int mode, int m, long long xbytes)
+{
+    if (mode == LQK_R2_FILTER) return LQK_R2_ROUTE_FILTER;
+    return m <= 16 && xbytes < (1ll << 31) ? LQK_R2_ROUTE_TILED_B : LQK_R2_ROUTE_TILED;
+}
+
 template <typename S, typename C>
 void run_r2(const R2Args &a, const void *taps, const void *h0, const void *h1, void *n0, void *n1, const void *x,
             void *y0, void *y1, hipStream_t st)
@@ -322,7 +330,9 @@ void run_r2(const R2Args &a, const void *taps, const void *h0, const void *h1, v
         break;
     default: p0 = p1 = a.n;
     }
-    if (a.mode == LQK_R2_FILTER) {
+    const long long xbytes = (a.mode == LQK_R2_INTERP || a.mode == LQK_R2_FILTER ? a.n : 2 * a.n) * (long long)sizeof(S);
+    const int route = r2_decide(a.mode, a.m, xbytes);
+    if (route == LQK_R2_ROUTE_FILTER) {
         const unsigned grid = (unsigned)((a.n + NT - 1) / NT);
         hipLaunchKernelGGL((k_resamp2<S, C>), dim3(grid), dim3(NT), (size_t)2 * a.m * sizeof(C), st, a,
                            (const C *)taps, (const S *)h0, (const S *)h1, (const S *)x, (S *)y0, (S *)y1);
@@ -330,8 +340,7 @@ void run_r2(const R2Args &a, const void *taps, const void *h0, const void *h1, v
         constexpr int R = 4, CT = NT * R;
         const size_t lds = ((2 * 2 * a.m * sizeof(C) + 15) & ~(size_t)15) + (size_t)(2 * CT + 2 * a.m) * sizeof(S);
         const unsigned grid = (unsigned)((a.n + CT - 1) / CT);
-        const long long xbytes = (a.mode == LQK_R2_INTERP ? a.n : 2 * a.n) * (long long)sizeof(S);
-        if (a.m <= 16 && xbytes < (1ll << 31)) {
+        if (route == LQK_R2_ROUTE_TILED_B) {
             switch (a.mode) {
 #define LQ_R2B(MD)                                                                                         \
     case MD:                                                                                               \
@@ -353,6 +362,18 @@ void run_r2(const R2Args &a, const void *taps, const void *h0, const void *h1, v
 }
 
 } // namespace
+
+extern "C" int lqk_resamp2_route(int mode, unsigned int m, unsigned long long xbytes)
+{
+    if (mode < LQK_R2_FILTER || mode > LQK_R2_INTERP || m == 0 || xbytes >= (1ull << 62)) return -1;
+    return r2_decide(mode, (int)m, (long long)xbytes);
+}
+
+extern "C" unsigned int lqk_resamp2_route_tile(int route)
+{
+    // calls per workgroup: k_resamp2 one per lane; the tiled kernels R = 4 per lane
+    return route == LQK_R2_ROUTE_FILTER ? NT : (route == LQK_R2_ROUTE_TILED_B || route == LQK_R2_ROUTE_TILED) ? 4 * NT : 0;
+}
 
 extern "C" void lqk_resamp2(int kind, int mode, unsigned int m, int t0, float scale, const void *taps,
                             const void *hist0, const void *hist1, void *hist0_new, void *hist1_new, const void *x,

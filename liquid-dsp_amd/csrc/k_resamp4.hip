@@ -555,6 +555,9 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
     }
 }
 
+// outputs a wave tile keeps: the fused stage's tiles overlap by its halo
+constexpr int rs4_ts(int hm) { return TOUT - (hm ? ((2 * hm - 1 + 3) & ~3) : 0); }
+
 template <int L, bool UP, int HM, bool R4 = false, bool DN = false>
 void launch_rs4_c(const lqk_rs4_plan &pl, unsigned long long g0, unsigned long long K0, int npfb, float del,
                   const float2 *taps2, const float2 *hist, const float2 *x, int n, float2 *y, int nout,
@@ -568,7 +571,7 @@ void launch_rs4_c(const lqk_rs4_plan &pl, unsigned long long g0, unsigned long l
     const int RS = npfb + 1;
     const size_t lds =
         (size_t)((rs4_rows<L, UP, DN>() * RS * 8 + 15) & ~15) + (size_t)(NT4 / 64) * 4 * rs4_n4<UP, DN>() * 8;
-    constexpr int TS = TOUT - (HM ? ((2 * HM - 1 + 3) & ~3) : 0);
+    constexpr int TS = rs4_ts(HM);
     const int ntiles = (nout + TS - 1) / TS;
     const int wgs = (ntiles + NT4 / 64 - 1) / (NT4 / 64);
     constexpr int B = HM ? 4 : rs4_blk<L, UP, DN>();   // the fused stage's window needs the VGPRs of a fifth
@@ -582,20 +585,35 @@ void launch_rs4_c(const lqk_rs4_plan &pl, unsigned long long g0, unsigned long l
                            taps2, hist, x, n, y, nout, smode, hb, hj);
 }
 
+// the rate class of an unfused launch: the one decision behind launch_rs4 and
+// lqk_resamp4_route
+int rs4_class(float del)
+{
+    if (del < 0.5f) return LQK_RS_ROUTE_RS4_UP_R4;   // r > 2: more than two outputs per input
+    if (del <= 1.0f) return LQK_RS_ROUTE_RS4_UP;
+    if (del >= 2.0f) return LQK_RS_ROUTE_RS4_DOWN_DN;   // 1/4 < r <= 1/2: an output every two to four inputs
+    return LQK_RS_ROUTE_RS4_DOWN;
+}
+
 template <int L>
 void launch_rs4(const lqk_rs4_plan &pl, unsigned long long g0, unsigned long long K0, int npfb, float del,
                 const float2 *taps2, const float2 *hist, const float2 *x, int n, float2 *y, int nout,
                 const lqk_hist_job &hj, hipStream_t st)
 {
     const lqk_rs4_hb none{};
-    if (del < 0.5f)   // r > 2: more than two outputs per input
+    switch (rs4_class(del)) {
+    case LQK_RS_ROUTE_RS4_UP_R4:
         launch_rs4_c<L, true, 0, true>(pl, g0, K0, npfb, del, taps2, hist, x, n, y, nout, none, hj, st);
-    else if (del <= 1.0f)
+        break;
+    case LQK_RS_ROUTE_RS4_UP:
         launch_rs4_c<L, true, 0>(pl, g0, K0, npfb, del, taps2, hist, x, n, y, nout, none, hj, st);
-    else if (del >= 2.0f)   // 1/4 < r <= 1/2: an output every two to four inputs
+        break;
+    case LQK_RS_ROUTE_RS4_DOWN_DN:
         launch_rs4_c<L, false, 0, false, true>(pl, g0, K0, npfb, del, taps2, hist, x, n, y, nout, none, hj, st);
-    else
+        break;
+    default:
         launch_rs4_c<L, false, 0>(pl, g0, K0, npfb, del, taps2, hist, x, n, y, nout, none, hj, st);
+    }
 }
 
 } // namespace
@@ -609,6 +627,12 @@ extern "C" int lqk_resamp4_supported(unsigned int npfb, unsigned int L)
 extern "C" int lqk_resamp4_hb_supported(unsigned int npfb, unsigned int L, float del, int m)
 {
     return npfb == 64 && L == 14 && del > 0.5f && del <= 1.0f && m >= 3 && m <= LQK_RS4_HB_MAXM;
+}
+
+extern "C" int lqk_resamp4_route(float del, int hm, unsigned int *tile)
+{
+    if (tile) *tile = (unsigned int)rs4_ts(hm);
+    return hm ? LQK_RS_ROUTE_RS4_UP : rs4_class(del);
 }
 
 extern "C" void lqk_resamp4(const lqk_rs4_plan *pl, unsigned long long g0, unsigned long long K0, unsigned int npfb,

@@ -248,6 +248,16 @@ typedef struct {
 void lqk_resamp(int real_io, const lqk_rs_plan *pl, unsigned long long g0, unsigned long long K0, unsigned int npfb,
                 unsigned int L, float del, const void *taps, const void *taps2, const void *hist, const void *x,
                 unsigned long long n, void *y, unsigned long long nout, void *stream);
+/* The kernel such a launch takes (with taps2 given) and, in *tile, its inputs
+ * per tile: k_resamp3 with the constant or the run-time pair-table stride
+ * (tin), k_resamp (8 x 256), k_resamp_generic (256); P, pre, end: the plan's.
+ * RS4_*: k_resamp4's rate classes, lqk_resamp4_route (256 outputs per tile) */
+enum {
+    LQK_RS_ROUTE_R3_CONST = 0, LQK_RS_ROUTE_R3_STRIDE, LQK_RS_ROUTE_RS, LQK_RS_ROUTE_GENERIC,
+    LQK_RS_ROUTE_RS4_UP, LQK_RS_ROUTE_RS4_UP_R4, LQK_RS_ROUTE_RS4_DOWN, LQK_RS_ROUTE_RS4_DOWN_DN
+};
+int lqk_resamp_route(int real_io, unsigned long long P, unsigned long long pre, unsigned long long end,
+                     unsigned int npfb, unsigned int L, float del, unsigned int *tile);
 /* taps2: (npfb+1) x LP pairs, LP = (L+3) & ~1: row b < npfb (h_b[L-p], h_{b+1}[L-p]) for p = 1..L, row
  * npfb the BOUNDARY pair (h_{npfb-1}[L-1-p], h_0[L-p]); zero elsewhere (NULL: untiled kernel) */
 /* Output plan of k_resamp4 (csrc/k_resamp4.hip: complex samples, power-of-two
@@ -286,6 +296,9 @@ typedef struct {
 int lqk_resamp4_supported(unsigned int npfb, unsigned int L);
 /* the fused chain's shapes: L = 14, npfb = 64, 1 < r < 2, m in 3 .. LQK_RS4_HB_MAXM */
 int lqk_resamp4_hb_supported(unsigned int npfb, unsigned int L, float del, int m);
+/* the rate class an unfused launch takes (LQK_RS_ROUTE_RS4_*) and, in *tile,
+ * the outputs per wave tile; hm > 0: of the fused chain (class UP), whose tiles are shorter by the stage's halo */
+int lqk_resamp4_route(float del, int hm, unsigned int *tile);
 /* n complex inputs x (plan inputs g0 .. g0+n) -> the nout outputs y[k - K0]
  * for plan outputs k = K0 .. K0+nout-1; taps2 and hist as lqk_resamp.  hb
  * (NULL: none): y receives the half-band stage's 2 nout outputs instead */
@@ -337,6 +350,10 @@ void lqk_spgram_db(int mode, const void *X, const float *v, unsigned int nfft, f
  * decim y0[i] (times scale, a power of two); analyzer/interp/synthesizer
  * y0[2i], y0[2i+1].  t0: filter-mode toggle before the first call. */
 enum { LQK_R2_FILTER = 0, LQK_R2_ANALYZER, LQK_R2_SYNTHESIZER, LQK_R2_DECIM, LQK_R2_INTERP };
+/* the kernel a launch of this mode, m and bytes of x takes (-1: bad arguments) and its calls per workgroup */
+enum { LQK_R2_ROUTE_FILTER = 0, LQK_R2_ROUTE_TILED_B, LQK_R2_ROUTE_TILED };
+int lqk_resamp2_route(int mode, unsigned int m, unsigned long long xbytes);
+unsigned int lqk_resamp2_route_tile(int route);
 void lqk_resamp2(int kind, int mode, unsigned int m, int t0, float scale, const void *taps, const void *hist0,
                  const void *hist1, void *hist0_new, void *hist1_new, const void *x, unsigned long long n,
                  void *y0, void *y1, void *stream);

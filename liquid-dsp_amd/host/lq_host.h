@@ -334,6 +334,12 @@ typedef struct {
 void lq_rs_block_dev_hb(lq_rs *q, const void *dx, unsigned long long nx, void *dy, unsigned long long *ny,
                         const lq_rs_hb *hb);
 lq_ctx *lq_rs_ctx(lq_rs *q);
+/* Host only: the kernel (LQK_RS_ROUTE_*) and tile of the first block call of
+ * nx inputs on a fresh engine, by the plan policy and launch decision the
+ * calls use; hm > 0: with a half-band stage of that semi-length behind it,
+ * *fused whether the launch takes the stage along.  -1: bad arguments */
+int lq_rs_route(int kind, float rate, unsigned int m, unsigned int npfb, unsigned long long nx, int hm,
+                unsigned int *tile, int *fused);
 
 /* ---- the oscillator's phase plan (host/nco_plan.c): float32 phase
  * arithmetic only -- no runtime call, no kernel launch, libc and libm alone */

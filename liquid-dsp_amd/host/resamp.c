@@ -99,6 +99,30 @@ static void rs_check_rate(lq_rs *q)
         LQ_FAIL("error: resamp_%s_execute(), invalid resampling rate (%f)\n", lq_ext(q->kind), q->rate);
 }
 
+/* The plan a call of nx inputs builds from `origin` (host only): which kind,
+ * and with it which kernel -- the one policy behind rs_ensure_plan and
+ * liquid_mi355x_resamp_route.  Returns how many of the inputs it covers. */
+static unsigned long long rs_new_plan(rs_plan *pl, int kind, float del, unsigned int npfb, unsigned int L,
+                                      rs_state origin, unsigned long long nx, int *periodic_failed, int *rate_changed)
+{
+    const int d4 = rs_want_d4(kind, del, npfb, L);
+    if (!*periodic_failed && nx >= RS_PERIODIC_MIN) {
+        if (rs_plan_build_periodic(pl, del, npfb, origin, d4)) return nx;
+        *periodic_failed = 1;
+    }
+    /* a direct plan covers this call and, for short calls, the next
+     * RS_DIRECT_AHEAD inputs too: the schedule does not depend on the data,
+     * so per-sample execute() calls reuse one plan instead of building and
+     * uploading one each (two stream synchronisations per call) */
+    unsigned long long c = nx < RS_DIRECT_CHUNK ? nx : RS_DIRECT_CHUNK;
+    /* right after a rate change the plan covers just this call: a loop that
+     * steers the rate before every call (symsync-style) would otherwise build
+     * RS_DIRECT_AHEAD inputs of schedule per call and use a fraction */
+    rs_build_direct(pl, kind, del, npfb, origin, (c > RS_DIRECT_AHEAD || *rate_changed) ? c : RS_DIRECT_AHEAD, d4);
+    *rate_changed = 0;
+    return c;
+}
+
 /* make the plan cover inputs [gpos, gpos + nx); returns how many of them it covers */
 static unsigned long long rs_ensure_plan(lq_rs *q, unsigned long long nx)
 {
@@ -109,25 +133,8 @@ static unsigned long long rs_ensure_plan(lq_rs *q, unsigned long long nx)
     rs_sync_now(q);                          /* the new plan starts where the old one's coverage ends */
     q->pl.valid = 0;
     q->gpos = 0;
-    const int d4 = rs_want_d4(q->kind, q->del, q->npfb, q->L);
-    if (!q->periodic_failed && nx >= RS_PERIODIC_MIN) {
-        if (rs_plan_build_periodic(&q->pl, q->del, q->npfb, q->now, d4)) {
-            rs_plan_upload(q);
-            return nx;
-        }
-        q->periodic_failed = 1;
-    }
-    /* a direct plan covers this call and, for short calls, the next
-     * RS_DIRECT_AHEAD inputs too: the schedule does not depend on the data,
-     * so per-sample execute() calls reuse one plan instead of building and
-     * uploading one each (two stream synchronisations per call) */
-    unsigned long long c = nx < RS_DIRECT_CHUNK ? nx : RS_DIRECT_CHUNK;
-    /* right after a rate change the plan covers just this call: a loop that
-     * steers the rate before every call (symsync-style) would otherwise build
-     * RS_DIRECT_AHEAD inputs of schedule per call and use a fraction */
-    rs_build_direct(&q->pl, q->kind, q->del, q->npfb, q->now,
-                    (c > RS_DIRECT_AHEAD || q->rate_changed) ? c : RS_DIRECT_AHEAD, d4);
-    q->rate_changed = 0;
+    const unsigned long long c = rs_new_plan(&q->pl, q->kind, q->del, q->npfb, q->L, q->now, nx, &q->periodic_failed,
+                                             &q->rate_changed);
     rs_plan_upload(q);
     return c;
 }
@@ -281,6 +288,12 @@ unsigned long long lq_rs_num_output(lq_rs *_q, unsigned long long _nx)
     return rs_count_outputs(rs_here(_q), _q->del, _q->npfb, _nx);
 }
 
+/* whether a launch on this plan takes a half-band stage of semi-length hm with it (k_resamp4's fused form) */
+static int rs_fuses(const rs_plan *pl, unsigned int npfb, unsigned int L, float del, int hm)
+{
+    return pl->dk == RS_D4 && lqk_resamp4_hb_supported(npfb, L, del, hm);
+}
+
 void lq_rs_block_dev(lq_rs *_q, const void *_dxv, unsigned long long _nx, void *_dyv, unsigned long long *_ny)
 {
     lq_rs_block_dev_hb(_q, _dxv, _nx, _dyv, _ny, NULL);
@@ -301,7 +314,7 @@ void lq_rs_block_dev_hb(lq_rs *_q, const void *_dxv, unsigned long long _nx, voi
         unsigned long long K0 = rs_K(_q, _q->gpos), K1 = rs_K(_q, _q->gpos + c);
         void *hold = lq_hist_dev(&_q->hist, _q->ctx.stream), *hnew = lq_hist_next(&_q->hist);
         const unsigned long long nk = K1 - K0;
-        const int fuse = hb && nk > 0 && _q->pl.dk == RS_D4 && lqk_resamp4_hb_supported(_q->npfb, _q->L, _q->del, hb->m);
+        const int fuse = hb && nk > 0 && rs_fuses(&_q->pl, _q->npfb, _q->L, _q->del, hb->m);
         /* an unfused chain chunk: the resampler's outputs through ubuf */
         char *uy = hb && !fuse ? (char *)lq_devbuf_get(&_q->ubuf, (size_t)(nk ? nk : 1) * _q->esz) : _dy;
         if (_q->pl.dk == RS_D4) {
@@ -462,6 +475,45 @@ static int rs_hook_plan(rs_plan *pl, float rate, unsigned int npfb, int periodic
     if (periodic) return rs_plan_build_periodic(pl, del, npfb, rs_initial, want);
     rs_build_direct(pl, kind, del, npfb, rs_initial, nx, want);
     return 1;
+}
+
+/* The kernel the first block call of nx inputs on a fresh object takes
+ * (LQK_RS_ROUTE_*, lq_kernels.h) and, in *_tile, its tile: inputs for the
+ * input-plan kernels, outputs for k_resamp4.  Host only: the plan that call
+ * would build (rs_new_plan) and the launch's own decision on it.  -1: bad
+ * arguments */
+_Static_assert((int)LIQUID_MI355X_RESAMP3_CONST == (int)LQK_RS_ROUTE_R3_CONST &&
+               (int)LIQUID_MI355X_RESAMP3_STRIDE == (int)LQK_RS_ROUTE_R3_STRIDE &&
+               (int)LIQUID_MI355X_RESAMP == (int)LQK_RS_ROUTE_RS &&
+               (int)LIQUID_MI355X_RESAMP_GENERIC == (int)LQK_RS_ROUTE_GENERIC &&
+               (int)LIQUID_MI355X_RESAMP4_UP == (int)LQK_RS_ROUTE_RS4_UP &&
+               (int)LIQUID_MI355X_RESAMP4_UP_R4 == (int)LQK_RS_ROUTE_RS4_UP_R4 &&
+               (int)LIQUID_MI355X_RESAMP4_DOWN == (int)LQK_RS_ROUTE_RS4_DOWN &&
+               (int)LIQUID_MI355X_RESAMP4_DOWN_DN == (int)LQK_RS_ROUTE_RS4_DOWN_DN, "route codes");
+
+int lq_rs_route(int kind, float rate, unsigned int m, unsigned int npfb, unsigned long long nx, int hm,
+                unsigned int *tile, int *fused)
+{
+    if (fused) *fused = 0;
+    if (kind < LQ_RRRF || kind > LQ_CCCF || !(rate > 0.0f) || m == 0 || npfb == 0 || nx == 0) return -1;
+    const float del = 1.0f / rate;
+    const unsigned int L = 2 * m;
+    rs_plan pl;
+    int periodic_failed = 0, rate_changed = 0;
+    rs_plan_init(&pl);
+    rs_new_plan(&pl, kind, del, npfb, L, rs_initial, nx, &periodic_failed, &rate_changed);
+    const int fuse = hm > 0 && rs_fuses(&pl, npfb, L, del, hm);
+    const int route = pl.dk == RS_D4 ? lqk_resamp4_route(del, fuse ? hm : 0, tile)
+                                     : lqk_resamp_route(kind == LQ_RRRF, pl.P, pl.pre, pl.end, npfb, L, del, tile);
+    if (fused) *fused = fuse;
+    rs_plan_free(&pl);
+    return route;
+}
+
+int liquid_mi355x_resamp_route(int _kind, float _rate, unsigned int _m, unsigned int _npfb, unsigned long long _nx,
+                               unsigned int *_tile)
+{
+    return lq_rs_route(_kind, _rate, _m, _npfb, _nx, 0, _tile, NULL);
 }
 
 /* Plan memory: the periodic plan's host checkpoint table allocation and the

@@ -226,6 +226,18 @@ LQ_RESAMP2_FRONT(resamp2_rrrf, LQ_RRRF, float)
 LQ_RESAMP2_FRONT(resamp2_crcf, LQ_CRCF, liquid_float_complex)
 LQ_RESAMP2_FRONT(resamp2_cccf, LQ_CCCF, liquid_float_complex)
 
+/* test hook (host only): the kernel a block call takes, by the launch's own decision */
+_Static_assert((int)LIQUID_MI355X_RESAMP2_K_FILTER == (int)LQK_R2_ROUTE_FILTER &&
+               (int)LIQUID_MI355X_RESAMP2_K_TILED_B == (int)LQK_R2_ROUTE_TILED_B &&
+               (int)LIQUID_MI355X_RESAMP2_K_TILED == (int)LQK_R2_ROUTE_TILED, "route codes");
+
+int liquid_mi355x_resamp2_route(int _mode, unsigned int _m, unsigned long long _bytes, unsigned int *_tile)
+{
+    const int route = lqk_resamp2_route(_mode, _m, _bytes);
+    if (_tile) *_tile = lqk_resamp2_route_tile(route);
+    return route;
+}
+
 /* =================================================================== msresamp2 */
 typedef struct {
     int kind, type;          /* LIQUID_RESAMP_INTERP / _DECIM */
@@ -243,6 +255,15 @@ static void lq_ms2_set_stream(lq_ms2 *q, void *s)
 {
     lq_ctx_set_stream(&q->ctx, s);
     for (unsigned int i = 0; i < q->ns; i++) lq_ctx_set_stream(&q->st[i]->ctx, q->ctx.stream);
+}
+
+/* semi-length of the stage with cut-off fc (msresamp2.c:137-150) */
+static unsigned int ms2_stage_m(float fc, float As)
+{
+    const float ft = (0.5f - fc) / 2.0f;
+    const unsigned int hl = estimate_req_filter_len(ft, As);
+    const unsigned int m = (unsigned int)ceilf((float)(hl - 1) / 4.0f);
+    return m < 3 ? 3 : m;
 }
 
 static lq_ms2 *lq_ms2_create(int kind, int type, unsigned int ns, float fc, float f0, float As)
@@ -272,13 +293,10 @@ static lq_ms2 *lq_ms2_create(int kind, int type, unsigned int ns, float fc, floa
     for (unsigned int i = 0; i < ns; i++) {   /* msresamp2.c:137-150 */
         f0 = 0.5f * f0;
         fc = 0.5f * fc;
-        const float ft = (0.5f - fc) / 2.0f;
-        const unsigned int hl = estimate_req_filter_len(ft, As);
-        const unsigned int m = (unsigned int)ceilf((float)(hl - 1) / 4.0f);
         q->fc_stage[i] = fc;
         q->f0_stage[i] = f0;
         q->As_stage[i] = As;
-        q->m_stage[i] = m < 3 ? 3 : m;
+        q->m_stage[i] = ms2_stage_m(fc, As);
         q->st[i] = lq_r2_create(kind, q->m_stage[i], f0, As);
         lq_ctx_set_stream(&q->st[i]->ctx, q->ctx.stream);
     }
@@ -419,6 +437,32 @@ static void lq_ms_set_stream(lq_ms *q, void *s)
     lq_ctx_set_stream(lq_rs_ctx(q->rs), q->ctx.stream);
 }
 
+/* msresamp.c:68-110: half-band stages until the arbitrary rate is in [1/2, 2] */
+static void ms_split(float r, int *type, unsigned int *ns, float *rate_arb, float *rate_hb)
+{
+    *type = r > 1.0f ? LIQUID_RESAMP_INTERP : LIQUID_RESAMP_DECIM;
+    *ns = 0;
+    *rate_arb = r;
+    *rate_hb = 1.0f;
+    if (*type == LIQUID_RESAMP_INTERP) {
+        while (*rate_arb > 2.0f) {
+            (*ns)++;
+            *rate_hb *= 2.0f;
+            *rate_arb *= 0.5f;
+        }
+    } else {
+        while (*rate_arb < 0.5f) {
+            (*ns)++;
+            *rate_hb *= 0.5f;
+            *rate_arb *= 2.0f;
+        }
+    }
+}
+
+/* the semi-length with which the first half-band stage applied joins the
+ * resampler's chain (lq_rs_block_dev_hb), 0: the chain's stages run on their own */
+static int ms_chain_m(int kind, unsigned int m) { return kind != LQ_RRRF && m <= LQK_RS4_HB_MAXM ? (int)m : 0; }
+
 static lq_ms *lq_ms_create(int kind, float r, float As)
 {
     if (r <= 0.0f) LQ_FAIL("error: msresamp_%s_create(), resampling rate must be greater than zero\n", lq_ext(kind));
@@ -427,22 +471,7 @@ static lq_ms *lq_ms_create(int kind, float r, float As)
     q->esz = kind == LQ_RRRF ? 4 : 8;
     q->rate = r;
     q->As = As;
-    q->type = r > 1.0f ? LIQUID_RESAMP_INTERP : LIQUID_RESAMP_DECIM;
-    q->rate_arb = r;
-    q->rate_hb = 1.0f;
-    if (q->type == LIQUID_RESAMP_INTERP) {
-        while (q->rate_arb > 2.0f) {
-            q->ns++;
-            q->rate_hb *= 2.0f;
-            q->rate_arb *= 0.5f;
-        }
-    } else {
-        while (q->rate_arb < 0.5f) {
-            q->ns++;
-            q->rate_hb *= 0.5f;
-            q->rate_arb *= 2.0f;
-        }
-    }
+    ms_split(r, &q->type, &q->ns, &q->rate_arb, &q->rate_hb);
     q->M = 1u << q->ns;
     lq_ctx_init(&q->ctx);
     q->hb = lq_ms2_create(kind, q->type, q->ns, 0.4f, 0.0f, As);
@@ -511,7 +540,7 @@ static void lq_ms_block_dev(lq_ms *q, const void *dx, unsigned long long nx, voi
         lq_r2 *h = q->ns ? q->hb->st[q->ns - 1] : NULL;   /* the first half-band stage applied */
         if (q->ns == 0) {
             lq_rs_block_dev(q->rs, dx, nx, dy, &n);
-        } else if (q->kind != LQ_RRRF && h->m <= LQK_RS4_HB_MAXM) {
+        } else if (ms_chain_m(q->kind, h->m)) {
             /* the resampler and the first half-band stage as one chain
              * (msresamp.c:289-300: every resampler output straight into the
              * half-band interpolator), the later stages after it */
@@ -614,6 +643,27 @@ static void lq_ms_block(lq_ms *q, const void *x, unsigned int nx, void *y, unsig
     }                                                                                               \
     void NAME##_set_stream(NAME _q, void *_s) { lq_ms_set_stream(_q->e, _s); }                      \
     void NAME##_synchronize(NAME _q) { lqrt_sync(_q->e->ctx.stream); }
+
+/* test hook (host only): the resampler kernel of an msresamp's first block
+ * call of _nx inputs and its tile, and in *_hm the semi-length of the half-band
+ * stage that launch takes along (0: none) -- by the functions the calls use */
+int liquid_mi355x_msresamp_route(int _kind, float _rate, float _As, unsigned long long _nx, unsigned int *_tile,
+                                 unsigned int *_hm)
+{
+    int type, fused = 0;
+    unsigned int ns;
+    float ra, rh;
+    if (_hm) *_hm = 0;
+    if (!(_rate > 0.0f)) return -1;
+    ms_split(_rate, &type, &ns, &ra, &rh);
+    int hm = 0;
+    float fc = 0.4f;
+    for (unsigned int i = 0; i < ns; i++) fc = 0.5f * fc;   /* stage ns - 1, the first one an interpolator applies */
+    if (type == LIQUID_RESAMP_INTERP && ns > 0) hm = ms_chain_m(_kind, ms2_stage_m(fc, _As));
+    const int route = lq_rs_route(_kind, ra, 7, 64, type == LIQUID_RESAMP_INTERP ? _nx : _nx >> ns, hm, _tile, &fused);
+    if (_hm && fused) *_hm = (unsigned int)hm;
+    return route;
+}
 
 LQ_MSRESAMP_FRONT(msresamp_rrrf, LQ_RRRF, float)
 LQ_MSRESAMP_FRONT(msresamp_crcf, LQ_CRCF, liquid_float_complex)

@@ -89,6 +89,42 @@ def firdecim_grid_cap(t, M, hlen, route):
     return int(lib().liquid_mi355x_firdecim_grid_cap(_KINDS[t], M, hlen, FIRDECIM_ROUTES.index(route)))
 
 
+# liquid_mi355x_resamp_route's and liquid_mi355x_resamp2_route's codes, by name
+RESAMP_ROUTES = ("resamp3/const", "resamp3/stride", "resamp/", "generic/", "resamp4/up", "resamp4/up_r4",
+                 "resamp4/down", "resamp4/down_dn")
+RESAMP2_ROUTES = ("filter", "tiled_b", "tiled")
+
+
+def resamp_route(t, rate, m, npfb, nx):
+    """(kernel/class, tile) of the first block call of nx inputs on a fresh
+    resamp object (no GPU call); the tile in inputs (resamp3, resamp,
+    generic) or outputs (resamp4).  Reads LQ_RESAMP_INPUT_PLAN as the object does."""
+    tile = C.c_uint(0)
+    r = lib().liquid_mi355x_resamp_route(_KINDS[t], rate, m, npfb, nx, C.byref(tile))
+    if r < 0:
+        raise ValueError("resamp_route: bad arguments")
+    return RESAMP_ROUTES[r], int(tile.value)
+
+
+def resamp2_route(mode, m, nbytes):
+    """(kernel, calls per tile) of a resamp2 block call reading nbytes of input."""
+    tile = C.c_uint(0)
+    r = lib().liquid_mi355x_resamp2_route(mode, m, nbytes, C.byref(tile))
+    if r < 0:
+        raise ValueError("resamp2_route: bad arguments")
+    return RESAMP2_ROUTES[r], int(tile.value)
+
+
+def msresamp_route(t, rate, As, nx):
+    """(kernel/class, tile, hm) of the resampler launch of an msresamp's first
+    block call of nx inputs; hm: the fused half-band stage's m, 0 if none."""
+    tile, hm = C.c_uint(0), C.c_uint(0)
+    r = lib().liquid_mi355x_msresamp_route(_KINDS[t], rate, As, nx, C.byref(tile), C.byref(hm))
+    if r < 0:
+        raise ValueError("msresamp_route: bad arguments")
+    return RESAMP_ROUTES[r], int(tile.value), int(hm.value)
+
+
 def header_functions():
     """Every function the public header declares (macros expanded by cpp)."""
     out = subprocess.check_output(["gcc", "-E", "-P", "-I", os.path.join(ROOT, "include"), HEADER],
@@ -455,6 +491,9 @@ def _declare(L):
         "liquid_mi355x_firdecim_route": (i, [i, u, u, i, ull]),
         "liquid_mi355x_firdecim_tile": (u, [i]),
         "liquid_mi355x_firdecim_grid_cap": (u, [i, u, u, i]),
+        "liquid_mi355x_resamp_route": (i, [i, f, u, u, ull, vp]),
+        "liquid_mi355x_resamp2_route": (i, [i, u, ull, vp]),
+        "liquid_mi355x_msresamp_route": (i, [i, f, f, ull, vp, vp]),
         "kaiser": (f, [u, u, f, f]),
         "hann": (f, [u, u]),
         "blackmanharris": (f, [u, u]),
@@ -1003,6 +1042,13 @@ class Resamp2(_Obj):
         y1 = np.zeros(n, _out_dtype(self.t))
         self._fn("_execute_block")(self.q, mode, ptr(x), n, ptr(y0), ptr(y1))
         return (y0, y1) if mode == RESAMP2_FILTER else y0
+
+    def run_dev(self, mode, dx, n, dy0, dy1=None):
+        """n consecutive calls of one mode on device pointers."""
+        self._fn("_execute_block_dev")(self.q, mode, dx, n, dy0, dy1)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
 
     def call(self, mode, x):
         """one call of the original per-call API"""
@@ -1652,6 +1698,16 @@ class MsResamp2(_Obj):
         self.t, self.typ, self.M = t, typ, 1 << ns
         self.prefix = self.family % t
         self.q = self._fn("_create")(typ, ns, fc, f0, As)
+
+    def reset(self):
+        self._fn("_reset")(self.q)
+
+    def execute_block_dev(self, dx, n, dy):
+        """n calls (n inputs when interpolating, n M when decimating) on device pointers."""
+        self._fn("_execute_block_dev")(self.q, dx, n, dy)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
 
     def execute_block(self, x):
         x = _samples(x, self.t)

@@ -32,6 +32,7 @@ import fir_bound as FB
 import golden_io as G
 import liquidmi as LQ
 import oracle_lib as O
+import resamp_bound as RB
 
 pytestmark = pytest.mark.gpu
 
@@ -331,9 +332,13 @@ def test_resamp_stream_at_three_workgroups(limit3, t, plan_kind, rate):
     finally:
         _plan_env_restore(old)
     assert ny == len(ref)
-    e = G.nrm_err(dy.to_array(x.dtype, ny), ref)
+    y = dy.to_array(x.dtype, ny)
+    e = G.nrm_err(y, ref)
     print("resamp %s %s r=%g: %d outputs, %.3g" % (t, plan_kind, rate, ny, e))
     assert e < NRM
+    # and output by output (tests/resamp_bound.py; its own streams, with level
+    # edges on the tile seams, run at three workgroups in test_gpu_resamp_bound.py)
+    RB.check_stream("%s %s r=%g at three workgroups" % (t, plan_kind, rate), rate, 7, 0.25, 60.0, 64, x, y)
 
 
 # ============================================================= firfilt, 64 taps
