@@ -218,11 +218,9 @@ extern "C" void lqk_dotprod_single(int kind, const void *h, unsigned int n, cons
 {
     hipStream_t st = (hipStream_t)stream;
     const float *hf = (const float *)h, *xf = (const float *)x;
-    switch (kind) {
-    case 0: hipLaunchKernelGGL(k_dot_single<0>, dim3(1), dim3(256), 0, st, hf, (int)n, xf, (float *)y, flag, seq); break;
-    case 1: hipLaunchKernelGGL(k_dot_single<1>, dim3(1), dim3(256), 0, st, hf, (int)n, xf, (float *)y, flag, seq); break;
-    case 2: hipLaunchKernelGGL(k_dot_single<2>, dim3(1), dim3(256), 0, st, hf, (int)n, xf, (float *)y, flag, seq); break;
-    default:
+    if (!lq_switch<0, 1, 2>(kind, [&](auto k) {
+            hipLaunchKernelGGL(k_dot_single<k>, dim3(1), dim3(256), 0, st, hf, (int)n, xf, (float *)y, flag, seq);
+        })) {
         fprintf(stderr, "error: dotprod: invalid kind %d\n", kind);
         exit(1);
     }
@@ -234,11 +232,7 @@ extern "C" void lqk_dotprod_batch(int kind, const void *h, unsigned int n, const
 {
     if (nvec == 0) return;
     hipStream_t st = (hipStream_t)stream;
-    switch (kind) {
-    case 0: launch<0>(h, n, X, (long long)stride, (long long)nvec, Y, st); break;
-    case 1: launch<1>(h, n, X, (long long)stride, (long long)nvec, Y, st); break;
-    case 2: launch<2>(h, n, X, (long long)stride, (long long)nvec, Y, st); break;
-    default:
+    if (!lq_switch<0, 1, 2>(kind, [&](auto k) { launch<k>(h, n, X, (long long)stride, (long long)nvec, Y, st); })) {
         fprintf(stderr, "error: dotprod: invalid kind %d\n", kind);
         exit(1);
     }

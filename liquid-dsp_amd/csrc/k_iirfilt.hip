@@ -491,9 +491,9 @@ void run_all(int kind, unsigned int nsec, const void *coef, const void *ladder, 
         void *yi = (char *)y + (MODE == DECIM ? i / M : i) * esz;
         const bool ok = lq_switch<1, 2, 4, 8>((int)lqk_iirfilt_maxsec(nsec), [&](auto ms) {
             constexpr int MS = decltype(ms)::value;
-            if (kind == 0) run_piece<0, MS, MODE>(nsec, coef, ladder, state, xi, m, (int)M, yi, work, st);
-            else if (kind == 1) run_piece<1, MS, MODE>(nsec, coef, ladder, state, xi, m, (int)M, yi, work, st);
-            else run_piece<2, MS, MODE>(nsec, coef, ladder, state, xi, m, (int)M, yi, work, st);
+            lq_switch<0, 1, 2>(kind, [&](auto k) {
+                run_piece<k, MS, MODE>(nsec, coef, ladder, state, xi, m, (int)M, yi, work, st);
+            });
         });
         if (!ok) lq_check(hipErrorInvalidValue, who, __FILE__, __LINE__);
     }

@@ -62,7 +62,7 @@ void lqk_dotprod_single(int kind, const void *h, unsigned int n, const void *x, 
 typedef struct {
     int kind;
     unsigned int hlen;       /* logical length */
-    unsigned int hc;         /* compile-time chunk class: 8,16,32,64 */
+    unsigned int hc;         /* compile-time chunk class: 16, 32, 64 */
     unsigned int nchunk;     /* padded length = hc*nchunk */
     const void *hpad;        /* device coefficients (float or float2) */
     float scale_re, scale_im;
@@ -110,8 +110,8 @@ void lqk_fir_single(const lqk_fir_desc *d, const void *win, void *y, unsigned *f
 /* ---------------------------------------------------------------- firdecim / firinterp
  * decim: y[o] = sum_k h[k] ext[o*M + phase - k]  (o < nout)
  * interp: y[i*M + p] = scale * sum_{l<L} h[p + l*M] ext[i - l]  (i < n) */
-void lqk_firdecim(const lqk_fir_desc *d, unsigned int M, const void *hist, const void *x,
-                  unsigned long long nout, void *y, void *stream);
+void lqk_firdecim(int kind, unsigned int hlen, const void *hpad /* hlen taps, natural order */, unsigned int M,
+                  const void *hist, const void *x, unsigned long long nout, void *y, void *stream);
 /* phase-layout decimator: hq = M x QC phase-major padded taps,
  * hq[r*QC + q] = h[q*M + r] (0 past hlen), QC = lqk_firdecim_ph_qc(M, hlen);
  * hist = the previous hl1 = hlen-1 inputs.  Returns -1 (nothing launched)

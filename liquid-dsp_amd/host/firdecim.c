@@ -57,7 +57,6 @@ typedef struct {
     unsigned int M, hlen;
     float *h;          /* host copy, hlen coefficients of csz bytes */
     float *hg;         /* reversed, expanded for the host path (lq_host_taps) */
-    lqk_fir_desc d;
     void *d_hpad;
     void *d_hq;        /* M x QC phase-major taps for the phase-layout kernel */
     unsigned int QC;
@@ -95,13 +94,6 @@ static lq_decim *lq_decim_create(int kind, unsigned int M, const float *h, unsig
     lq_hist_init(&q->hist, hlen - 1, q->esz, LQ_HIST_MIRROR);
     lqrt_sync(q->ctx.stream);
     free(hq);
-    q->d.kind = kind;
-    q->d.hlen = hlen;
-    q->d.hc = hlen; /* the decimator kernel takes HP = hc * nchunk directly */
-    q->d.nchunk = 1;
-    q->d.hpad = q->d_hpad;
-    q->d.scale_re = 1.0f;
-    q->d.scale_im = 0.0f;
     return q;
 }
 
@@ -135,7 +127,7 @@ static void lq_decim_block_dev(lq_decim *q, const void *dx, unsigned long long n
     if (nout == 0) return;
     void *hold = lq_hist_dev(&q->hist, q->ctx.stream), *hnew = lq_hist_next(&q->hist);
     if (lqk_firdecim_ph(q->kind, q->M, q->QC, q->d_hq, q->hlen - 1, hold, dx, nout, dy, q->ctx.stream) != 0)
-        lqk_firdecim(&q->d, q->M, hold, dx, nout, dy, q->ctx.stream);
+        lqk_firdecim(q->kind, q->hlen, q->d_hpad, q->M, hold, dx, nout, dy, q->ctx.stream);
     if (q->hlen > 1) lqk_window_append(q->kind != LQ_RRRF, hold, q->hlen - 1, dx, nout * q->M, hnew, q->ctx.stream);
     lq_hist_flip(&q->hist);
 }

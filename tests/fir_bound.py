@@ -185,18 +185,20 @@ def decim_reference(t, h, x, M):
     return y64, A
 
 
-def decim_envelope(name, M, nout, cut):
+def decim_envelope(name, M, nout, cut, tile=512):
     """burst (1e-5 between the bursts) or gaps (exact zeros) over nout M input
     samples, the edges of the bursts on the seams of the decimator's tiles:
     256 and 512 outputs, that is multiples of a = 256 M and b = 512 M input
     samples, and one sample either side; one burst ends with the last input
     of the first `cut` outputs, so a call that starts at output `cut` sees it
-    only through the carried history; one runs to the end of the stream."""
+    only through the carried history; one runs to the end of the stream.
+    tile = 64 puts the seams at 32 and 64 outputs instead, for streams of a
+    few of the 64-output kernel's tiles."""
     assert name in ("burst", "gaps")
-    n, a, b = nout * M, 256 * M, 512 * M
-    assert nout >= 3 * 512 + 1 and 512 < cut < nout - 512
+    n, a, b = nout * M, tile // 2 * M, tile * M
+    assert nout >= 3 * tile + 1 and tile < cut < nout - tile
     e = np.full(n, 1e-5 if name == "burst" else 0.0)
-    mid = max(2, nout // 512 // 2) * b   # a seam of both tile sizes far from the start
+    mid = max(2, nout // tile // 2) * b   # a seam of both tile sizes far from the start
     for lo, hi in ((0, 40), (a - 50, a + 1), (b - 1, b + 60), (3 * a + 1, 3 * a + 300), (2 * b - 200, 2 * b - 1),
                    (5 * a, 5 * a + 1), (mid - 1, mid + 1), (cut * M - 300, cut * M),
                    (n - 3 * M - 1, n)):
@@ -214,9 +216,9 @@ DECIM_SMALL = (3 * 512 + 77, 700)   # (outputs, cut) of the small versions the o
 
 
 class DecimCase:
-    def __init__(self, t, M, hlen, name, nout, cut):
+    def __init__(self, t, M, hlen, name, nout, cut, tile=512):
         self.t, self.M, self.hlen, self.name, self.nout, self.cut = t, M, hlen, name, nout, cut
-        self.h, self.x = signal(t, hlen, "decim %d %s" % (M, name), decim_envelope(name, M, nout, cut))
+        self.h, self.x = signal(t, hlen, "decim %d %s" % (M, name), decim_envelope(name, M, nout, cut, tile))
         self.y64, self.A = decim_reference(t, self.h, self.x, M)
         for a in (self.x, self.y64, self.A):
             a.setflags(write=False)
@@ -225,10 +227,10 @@ class DecimCase:
         return check(self.t, self.hlen, y, self.y64, self.A)
 
 
-def decim_case(t, M, hlen, name, nout, cut):
+def decim_case(t, M, hlen, name, nout, cut, tile=512):
     """Not cached: a large-M case is a few hundred megabytes; its one test
     runs every cut of the stream against it."""
-    return DecimCase(t, M, hlen, name, nout, cut)
+    return DecimCase(t, M, hlen, name, nout, cut, tile)
 
 
 def report(t, hlen, y, y64, A):

@@ -293,7 +293,10 @@ def test_firdecim_device_path_unaligned(t):
 
 
 @pytest.mark.parametrize("t", ["rrrf", "crcf", "cccf"])
-@pytest.mark.parametrize("M,m", [(2, 3), (4, 3), (8, 5), (32, 2)])
+# M = 4, m = 7, 9, 11, 15: 2m + 1 taps per phase, the register-window kernel's
+# 16-, 20-, 24- and 32-tap classes (the rows before reach 8 and 12); m = 16:
+# 33 per phase, real taps on the plain kernel
+@pytest.mark.parametrize("M,m", [(2, 3), (4, 3), (8, 5), (32, 2), (4, 7), (4, 9), (4, 11), (4, 15), (4, 16)])
 def test_firinterp_vs_oracle(M, m, t):
     r = rng(M + 1)
     x = samples(r, t, 5000)

@@ -156,7 +156,7 @@ def test_firdecim_refuses_what_no_tile_holds():
     assert "created" in p.stdout and "ran" not in p.stdout
 
 
-# the three persistent launch shapes (k_firfilt.hip, decim_decide): four
+# the three persistent launch shapes (k_firdecim.hip, decim_decide): four
 # outputs per lane on 128 lanes, two on 256, one on 256
 @pytest.mark.parametrize("f,route", [(("rrrf", 2, 80), "pf_r4x128"), (("crcf", 8, 128), "pf_r2x256"),
                                      (("crcf", 16, 128), "pf_r1x256")], ids=["pf_r4x128", "pf_r2x256", "pf_r1x256"])
@@ -177,6 +177,46 @@ def test_firdecim_bound_at_the_real_cap(f, route):
     r = c.check(_decim_run(c, 0))
     print("firdecim real cap %s: cap %d x %d outputs, nout %d, worst %.3g of the bound; reference %.1f s, "
           "GPU call and check %.1f s" % (route, cap, TO, nout, r["worst"], t1 - t0, time.time() - t1))
+
+
+# k_firdecim_pf's deepest prefetch class (k_firdecim.hip, lqk_firdecim_ph: NL =
+# 5, 9 or 12 vectors per lane by nl <= 5, <= 9, else): the route table's rows
+# give nl of at most 9
+@pytest.mark.parametrize("M,hlen,route,lanes", [(4, 270, "pf_r4x128", 128), (8, 541, "pf_r2x256", 256),
+                                                (16, 571, "pf_r1x256", 256)], ids=["pf_r4x128", "pf_r2x256", "pf_r1x256"])
+def test_firdecim_pf_deepest_prefetch(limit3, M, hlen, route, lanes):
+    """crcf, 16-byte aligned x.  A lane stages nl = ceil(((TO + QC - 1) M + 1)
+    / (lanes * samples per 16 bytes)) vectors per tile, TO the route's tile,
+    QC the taps per phase rounded up to four, two crcf samples per 16 bytes:
+    10 at each of these shapes, so the kernel with NL = 12 runs and its last
+    two vectors are past the tile.  nout = 7 TO + 17: each of the three
+    workgroups walks more than one tile and the last tile is ragged."""
+    TO = LQ.firdecim_tile(route)
+    QC = (-(-hlen // M) + 3) // 4 * 4
+    nl = -(-((TO + QC - 1) * M + 1) // (lanes * 2))
+    assert 9 < nl <= 12
+    nout = 7 * TO + 17
+    assert LQ.firdecim_route("crcf", M, hlen, True, nout) == route
+    c = FB.decim_case("crcf", M, hlen, "burst", nout, nout // 2)
+    r = c.check(_decim_run(c, 0))
+    print("firdecim %s M=%d h=%d nl=%d: worst %.3g of the bound" % (route, M, hlen, nl, r["worst"]))
+
+
+# k_firdecim_ph's tap chunk classes (k_firdecim.hip, lqk_firdecim_ph): QC = 4,
+# 8, 16 or 32 taps per phase run as one chunk, any other QC in chunks of 16 if
+# 16 divides it, else of 4.  The route table's rows reach QC = 8 only.
+@pytest.mark.parametrize("hlen,QC", [(100, 4), (380, 12), (500, 16), (1000, 32), (1530, 48)])
+def test_firdecim_ph_chunk_classes(hlen, QC):
+    """crcf M = 32 on the 64-output kernel, aligned and one element off: three
+    tiles and a ragged fourth, bursts on the 64-output seams."""
+    M, nout = 32, 3 * 64 + 17
+    assert (-(-hlen // M) + 3) // 4 * 4 == QC
+    for aligned in (True, False):
+        assert LQ.firdecim_route("crcf", M, hlen, aligned, nout) == "ph_r1x64"
+    c = FB.decim_case("crcf", M, hlen, "burst", nout, 100, tile=64)
+    for off in (0, 1):
+        r = c.check(_decim_run(c, off))
+        print("firdecim ph_r1x64 M=%d h=%d QC=%d off=%d: worst %.3g of the bound" % (M, hlen, QC, off, r["worst"]))
 
 
 # ========================================================== batched transforms
