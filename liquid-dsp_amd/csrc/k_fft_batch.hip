@@ -93,7 +93,7 @@ __global__ __launch_bounds__(256) void k_fft1024_batch(const float2 *__restrict_
             if (use_s2) val = val * s2;
             yb[o >> 1] = val;
         }
-        f1k_wave_fence();   // B is reused by the next transform of this wave
+        lq_wave_fence();   // B is reused by the next transform of this wave
     }
 }
 

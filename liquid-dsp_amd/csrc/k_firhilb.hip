@@ -33,13 +33,13 @@ static_assert(CT == LQK_FIRHILB_TILE, "tile size is part of the interface (tests
 
 typedef float v2nt __attribute__((ext_vector_type(2)));
 
-// Range-checked view of `count` elements of `esz` bytes from p: loads past
-// the end (or at a negative element, whose 32-bit offset is huge) return 0.
-// The view is made per tile, so offsets stay within a tile plus its halo and
-// a launch has no length limit of its own.
+// Range-checked view (lq_buf) of `count` elements of `esz` bytes from p: loads
+// past the end (or at a negative element, whose 32-bit offset is huge) return
+// 0.  The view is made per tile, so offsets stay within a tile plus its halo
+// and a launch has no length limit of its own.
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t fh_view(const void *p, long long count, int esz)
 {
-    return __builtin_amdgcn_make_buffer_rsrc((void *)p, (short)0, (int)(count * esz), 0x00020000);
+    return lq_buf(p, (int)(count * esz));
 }
 
 // n calls of decim / interp.  Tile i0: the elements c = i0 - W + u, u < CT + W,
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(NT) void k_firhilb_pair(int m, long long n, const f
     const __amdgpu_buffer_rsrc_t rx = fh_view(x + cb, left < CT + W ? left : CT + W, 8);
     auto ld = [&](int u) -> float2 {
         const unsigned off = (unsigned)(int)((c0 - cb + u) * 8);
-        return __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rx, off, 0, 0));
+        return lq_buf_ld<float2>(rx, off);
     };
     for (int j = t; j < W; j += NT) th[j] = taps[j];
     // all of a lane's loads are issued before its first LDS store (the loop
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(NT) void k_firhilb_r2c(int m, int t0, long long n, 
     const __amdgpu_buffer_rsrc_t rx = fh_view(x + eb, left < CT + 2 * W ? left : CT + 2 * W, 4);
     auto ld = [&](int u) -> float {
         const unsigned off = (unsigned)(int)((e0 - eb + u) * 4);
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, off, 0, 0));
+        return lq_buf_ld<float>(rx, off);
     };
     auto slot = [&](int u) -> float * { return ((u & 1) ? s1 : s0) + (u >> 1); };
     for (int j = t; j < W; j += NT) th[j] = taps[j];

@@ -1,5 +1,5 @@
-// k_resamp.hip -- arbitrary-rate polyphase resampler (resamp_crcf) and the
-// per-sample firpfb_crcf output.
+// k_resamp.hip -- arbitrary-rate polyphase resampler (resamp_rrrf / _crcf /
+// _cccf) from an input plan: k_resamp3, k_resamp and k_resamp_generic.
 //
 // Reference: src/filter/src/resamp.c:245-363 (execute, update_timing_state),
 // src/filter/src/firpfb.c:325-345 (bank output).  For input t the reference
@@ -11,25 +11,29 @@
 //
 // Parallel form.  The timing state at the start of every input is a pure
 // function of the previous one (it does not depend on the data), so the host
-// tabulates it once per rate (`plan`, see host/resamp.c): checkpoint c holds
-// the state before input LQK_RS_CK c (LQK_RS_CK = 4) and K = outputs emitted
-// by the inputs before it -- (tau, K), 8 B, for power-of-two bank counts with
-// del >= 1/npfb (the rest of the state follows from tau), else
+// tabulates it once per rate (`plan`, see host/resamp_plan.c): checkpoint c
+// holds the state before input LQK_RS_CK c (LQK_RS_CK = 4) and K = outputs
+// emitted by the inputs before it -- (tau, K), 8 B, for power-of-two bank
+// counts with del >= 1/npfb (the rest of the state follows from tau), else
 // (tau, mu, b, state, K), 16 B; the sequence is eventually periodic
 // (pre-period `pre`, period `P` inputs, `Q` outputs per period; r = 1.037:
 // 253 K checkpoints, 2 MB, read from L2 at 2 B / input).  Lanes read
 // the checkpoint at or before their first input, step
 // the reference's float32 recurrence forward to it and replay their own
-// inputs, bit-exactly (contraction off).  Complex streams at 1 < r < 2 with a
-// power-of-two bank count run k_resamp4 (csrc/k_resamp4.hip, an output plan
-// instead); every other shape comes here: k_resamp3 turns the replay into a
-// dense per-wave-tile output list and evaluates it with coalesced stores;
-// k_resamp / k_resamp_generic cover shapes whose tables do not fit LDS and
-// rates whose outputs overflow a wave tile (r > ~52).
+// inputs, bit-exactly (contraction off; the recurrence is rs_input and
+// rs_skip_p2 of lq_resamp.h, written once).  Complex streams at 1/4 < r <= npfb
+// with a power-of-two bank count run k_resamp4 (csrc/k_resamp4.hip, an output
+// plan instead); every other shape comes here: k_resamp3 turns the replay
+// into a dense per-wave-tile output list and evaluates it with coalesced
+// stores; k_resamp (taps in LDS, L even up to 32) and k_resamp_generic (any
+// L) cover shapes whose tables do not fit k_resamp3's LDS and rates whose
+// outputs overflow a wave tile (r > ~52).  The per-sample firpfb output is
+// k_fir_single (csrc/k_firfilt.hip).
 #include <hip/hip_runtime.h>
 
 #include "lq_device.h"
 #include "lq_kernels.h"
+#include "lq_resamp.h"
 
 #include <cmath>
 #include <cstdio>
@@ -40,11 +44,6 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int RS_R = 8;
-
-struct rs_state {
-    float tau, mu;
-    int b, st; // st: 1 INTERP, 0 BOUNDARY
-};
 
 // sample-type helpers: real (rrrf) or complex (crcf, cccf) samples, real taps
 // (resamp.c:117-132 designs real taps for every type)
@@ -59,34 +58,12 @@ __device__ __forceinline__ float2 rs_mix(float c0, float2 a, float mu, float2 b)
 }
 __device__ __forceinline__ float rs_mix(float c0, float a, float mu, float b) { return c0 * a + mu * b; }
 
-// the reference's update_timing_state (resamp.c:352-363), IEEE float32, no FMA
-__device__ __forceinline__ void rs_advance(rs_state &s, float del, float fnpfb)
-{
-#pragma clang fp contract(off)
-    s.tau = s.tau + del;
-    const float bf = s.tau * fnpfb;
-    const float fb = __builtin_floorf(bf);
-    s.b = (int)fb;
-    s.mu = bf - fb;
-}
-
-// one input of the timing recurrence (resamp.c:253-307) without the data
-// path; returns the number of outputs it emits
+// one input of the timing recurrence without the data path; returns the
+// number of outputs it emits
 __device__ __forceinline__ unsigned rs_step(rs_state &s, float del, float fnpfb, int npfb)
 {
     unsigned n = 0;
-    while ((unsigned)s.b < (unsigned)npfb) {   // unsigned, as resamp.c:254 (int b vs unsigned npfb)
-        if (s.st && s.b == npfb - 1) {
-            s.st = 0;
-            s.b = npfb;
-            break;
-        }
-        n++;
-        rs_advance(s, del, fnpfb);
-        s.st = 1;
-    }
-    s.tau -= 1.0f;
-    s.b = (int)((unsigned)s.b - (unsigned)npfb);
+    rs_input(s, del, fnpfb, npfb, [&](const rs_state &) { n++; });
     return n;
 }
 
@@ -98,39 +75,15 @@ __device__ __forceinline__ void rs_entry(const lqk_rs_entry &e, rs_state &s)
     s.st = e.bst & 1;
 }
 
-// the state a power-of-two bank count derives from tau (host/resamp.c
-// rs_from_tau): BOUNDARY iff tau < 0, b = floor(tau npfb), mu its fraction
-__device__ __forceinline__ void rs_derive(float tau, float fnpfb, rs_state &s)
-{
-#pragma clang fp contract(off)
-    const float bf = tau * fnpfb;
-    const float fb = __builtin_floorf(bf);
-    s.tau = tau;
-    s.mu = bf - fb;
-    s.st = tau >= 0.0f ? 1 : 0;
-    s.b = s.st ? (int)fb : 0;
-}
-
 // the checkpoint (its fields in e) stepped `skip` inputs forward; K counts
-// the outputs of those inputs.  Power-of-two banks step tau alone: add del
-// until tau reaches 1 - 1/npfb, subtract 1 (host/resamp.c rs_step_p2)
+// the outputs of those inputs.  Power-of-two banks step tau alone
 __device__ __forceinline__ void rs_skip(const lqk_rs_entry &e, int p2, int skip, float del, float fnpfb, int npfb,
                                         rs_state &s, unsigned long long &K)
 {
     if (p2) {
-#pragma clang fp contract(off)
-        const float z = 1.0f - 1.0f / fnpfb;
-        float x = e.tau;
         unsigned k = 0;
-        for (int i = 0; i < skip; i++) {
-            while (x < z) {
-                x = x + del;
-                k++;
-            }
-            x = x - 1.0f;
-        }
+        rs_derive(rs_skip_p2(e.tau, skip, del, 1.0f - 1.0f / fnpfb, k), fnpfb, s);
         K += k;
-        rs_derive(x, fnpfb, s);
     } else {
         rs_entry(e, s);
         for (int i = 0; i < skip; i++) K += rs_step(s, del, fnpfb, npfb);
@@ -194,14 +147,9 @@ __global__ __launch_bounds__(NT) void k_resamp(lqk_rs_plan pl, unsigned long lon
 #pragma unroll
     for (int r = 0; r < RS_R; ++r) {
         if (i0 + r >= n) break;
-        while ((unsigned)s.b < (unsigned)npfb) {
-            if (s.st && s.b == npfb - 1) { // last filter: finish with the next input
-                s.st = 0;
-                s.b = npfb;
-                break;
-            }
-            const bool bnd = !s.st;
-            const float2 *tp = stp + (bnd ? npfb - 1 : s.b) * L;
+        rs_input(s, del, fnpfb, npfb, [&](const rs_state &c) {
+            const bool bnd = !c.st;
+            const float2 *tp = stp + (bnd ? npfb - 1 : c.b) * L;
             S a0{}, a1{};
 #pragma unroll
             for (int k = 0; k < L; ++k) {
@@ -211,12 +159,8 @@ __global__ __launch_bounds__(NT) void k_resamp(lqk_rs_plan pl, unsigned long lon
                 a0 = rs_axpy(t.x, xa, a0);
                 a1 = rs_axpy(t.y, xb, a1);
             }
-            *yo++ = rs_mix(1.0f - s.mu, a0, s.mu, a1);
-            rs_advance(s, del, fnpfb);
-            s.st = 1;
-        }
-        s.tau -= 1.0f;
-        s.b = (int)((unsigned)s.b - (unsigned)npfb);
+            *yo++ = rs_mix(1.0f - c.mu, a0, c.mu, a1);
+        });
     }
 }
 
@@ -253,23 +197,6 @@ constexpr int RS_STAUX = 2;
 // pair-table row stride (8-byte slots per half row): RSC, or npfb/2 + 1 at run time
 template <int RSC>
 __host__ __device__ inline int rs2_rs(int npfb) { return RSC ? RSC : (npfb >> 1) + 1; }
-// one LDS read of T as a relaxed workgroup-scope atomic: the compiler issues
-// it as its own ds_read_b64 / _b32 (2 LDS cycles per wave) and never pairs two
-// into a ds_read2_b64 (8 cycles, CDNA4 LDS table), and still batches them
-template <typename T>
-__device__ __forceinline__ T lds_rd(const T *p)
-{
-    if constexpr (sizeof(T) == 8) {
-        const unsigned long long u = __hip_atomic_load(reinterpret_cast<unsigned long long *>(const_cast<T *>(p)),
-                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return __builtin_bit_cast(T, u);
-    } else {
-        const unsigned u = __hip_atomic_load(reinterpret_cast<unsigned *>(const_cast<T *>(p)), __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_WORKGROUP);
-        return __builtin_bit_cast(T, u);
-    }
-}
-
 // acc + c w for a real coefficient and a complex (packed FMA) or real sample
 __device__ __forceinline__ float2 rs_fma(float c, float2 w, float2 acc)
 {
@@ -278,17 +205,6 @@ __device__ __forceinline__ float2 rs_fma(float c, float2 w, float2 acc)
     return make_float2(a2.x, a2.y);
 }
 __device__ __forceinline__ float rs_fma(float c, float w, float acc) { return fmaf(c, w, acc); }
-
-// stores through the output descriptor (an offset past it is dropped)
-__device__ __forceinline__ void rs_store1(__amdgpu_buffer_rsrc_t r, unsigned off, float2 v)
-{
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, off, 0, RS_STAUX);
-}
-__device__ __forceinline__ void rs_store1(__amdgpu_buffer_rsrc_t r, unsigned off, float v)
-{
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, off, 0, RS_STAUX);
-}
 
 // any L (window and taps read through the caches), one input per lane
 template <typename S>
@@ -307,10 +223,9 @@ __global__ __launch_bounds__(NT) void k_resamp_generic(lqk_rs_plan pl, unsigned 
     rs_lookup(pl, g0 + (unsigned long long)i, del, fnpfb, npfb, s, K);
     S *yo = y + (K - K0);
     auto X = [&](long long idx) -> S { return idx < 0 ? hist[L + idx] : x[idx]; };
-    while ((unsigned)s.b < (unsigned)npfb) {
-        if (s.st && s.b == npfb - 1) break;
-        const bool bnd = !s.st;
-        const float2 *tp = taps + (size_t)(bnd ? npfb - 1 : s.b) * L;
+    rs_input<false>(s, del, fnpfb, npfb, [&](const rs_state &c) {
+        const bool bnd = !c.st;
+        const float2 *tp = taps + (size_t)(bnd ? npfb - 1 : c.b) * L;
         S a0{}, a1{};
         for (int k = 0; k < L; ++k) {
             const float2 t = tp[k];
@@ -319,10 +234,8 @@ __global__ __launch_bounds__(NT) void k_resamp_generic(lqk_rs_plan pl, unsigned 
             a0 = rs_axpy(t.x, xa, a0);
             a1 = rs_axpy(t.y, xb, a1);
         }
-        *yo++ = rs_mix(1.0f - s.mu, a0, s.mu, a1);
-        rs_advance(s, del, fnpfb);
-        s.st = 1;
-    }
+        *yo++ = rs_mix(1.0f - c.mu, a0, c.mu, a1);
+    });
 }
 
 // ------------------------------------------------------------ wave tiles
@@ -347,25 +260,29 @@ __global__ __launch_bounds__(NT) void k_resamp_generic(lqk_rs_plan pl, unsigned 
 //     ds_read2_b64; non-temporal 8-byte stores through a descriptor over the
 //     launch's outputs.
 // Waves drift apart freely instead of meeting at two workgroup barriers per
-// 1024-input tile, as the round-3 form (k_resamp2: wave 0 replayed 16-input
-// spans for all four waves) did: 0.197 -> 0.184 ms per 2^25 inputs at
+// 1024-input tile, as the round-3 form (wave 0 replayed 16-input spans for
+// all four waves) did: 0.197 -> 0.184 ms per 2^25 inputs at
 // r = 1.037 on one box.
 constexpr int RS3_BLK = 5;       // resident workgroups per CU (four and six measured slower, round 4)
 constexpr int NT3 = 256;         // threads per k_resamp3 workgroup (waves own their tiles)
 constexpr int W3_TIN = 64 * 4;   // inputs per wave tile (64 lanes x 4)
 constexpr int W3_CAP = 320;      // output slots per wave tile
 constexpr int RS3_FIT = 15;      // a tile's fixed cost in evaluation passes x 10 (tile fitting, launch_rs)
-// table rows (float2 units) of k_resamp3
-template <int L>
-constexpr int rs3_rows() { return L + 1; }
-// dynamic LDS of k_resamp3: the pair table at row stride rs, then per wave
-// the window of ssz-byte samples and the output descriptors
-inline size_t rs3_lds_bytes(int L, size_t ssz, int rs)
-{
-    const int TS = W3_TIN + L + 2;
-    return (size_t)2 * (L + 1) * rs * sizeof(float2) +
-           (size_t)(NT3 / 64) * (((TS + 2) * ssz + 15) / 16 * 16 + (W3_CAP + 2) * 8);
-}
+// dynamic LDS of k_resamp3 for L taps and ssz-byte samples: the pair table
+// (2 (L + 1) rows at the run-time row stride rs), then per wave the window
+// and the output descriptors.  The kernel and rs_decide both read it here
+struct rs3_lds {
+    int rows;   // table rows per bank parity, float2 units
+    int ts;     // window samples of a tile
+    int dsc;    // byte offset of the descriptors in a wave's region (dsc[W3_CAP]: sink)
+    int wb;     // bytes per wave
+    __host__ __device__ constexpr rs3_lds(int L, int ssz)
+        : rows(L + 1), ts(W3_TIN + L + 2), dsc(((ts + 2) * ssz + 15) / 16 * 16), wb(dsc + (W3_CAP + 2) * 8)
+    {
+    }
+    __host__ __device__ constexpr size_t waves(int rs) const { return (size_t)2 * rows * rs * sizeof(float2); }
+    __host__ __device__ constexpr size_t bytes(int rs) const { return waves(rs) + (size_t)(NT3 / 64) * wb; }
+};
 
 template <int L, typename S, int RSC>
 __global__ __launch_bounds__(NT3, RS3_BLK) void k_resamp3(lqk_rs_plan pl, unsigned long long g0, unsigned long long K0,
@@ -375,12 +292,10 @@ __global__ __launch_bounds__(NT3, RS3_BLK) void k_resamp3(lqk_rs_plan pl, unsign
 {
     static_assert(LQK_RS_CK == 4, "k_resamp3 replays 4 inputs per lane from their own checkpoint");
     constexpr int SPAN = 4;
-    constexpr int LP = (L + 2 + 1) & ~1;          // pair stride of taps2 (host layout)
-    constexpr int TS = W3_TIN + L + 2;            // window samples of a tile
-    constexpr int WB = ((TS + 2) * (int)sizeof(S) + 15) / 16 * 16 + (W3_CAP + 2) * 8;   // bytes per wave
+    constexpr rs3_lds LY(L, (int)sizeof(S));
+    constexpr int TS = LY.ts, NROW = LY.rows;
     constexpr int NXV = (TS + 63) / 64;           // window samples per lane
     constexpr int NSLOT = W3_CAP / 64;            // output slots per lane
-    constexpr int NROW = rs3_rows<L>();
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int RS = rs2_rs<RSC>(npfb);
     float2 *tpl = reinterpret_cast<float2 *>(smem);
@@ -388,32 +303,23 @@ __global__ __launch_bounds__(NT3, RS3_BLK) void k_resamp3(lqk_rs_plan pl, unsign
     // tile-level quantity (tile, i0, the plan position and its 64-bit period
     // division) is wave-uniform and computes it on the scalar unit
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    unsigned char *wbase = smem + (size_t)2 * NROW * RS * sizeof(float2) + (size_t)wave * WB;
+    unsigned char *wbase = smem + LY.waves(RS) + (size_t)wave * LY.wb;
     S *cw = reinterpret_cast<S *>(wbase);
-    uint2 *dsc = reinterpret_cast<uint2 *>(wbase + ((TS + 2) * (int)sizeof(S) + 15) / 16 * 16);   // dsc[W3_CAP]: sink
+    uint2 *dsc = reinterpret_cast<uint2 *>(wbase + LY.dsc);
     const float fnpfb = (float)npfb;
     for (int t = tid; t < (npfb + 1) * NROW; t += NT3) {
         const int b = t / NROW, p = t % NROW;
-        const float2 v = taps2[b * LP + p];
-        tpl[(2 * p + (b & 1)) * RS + (b >> 1)] = make_float2(v.x, v.y - v.x);
+        tpl[(2 * p + (b & 1)) * RS + (b >> 1)] = rs_pair(taps2, b * rs_lp<L>() + p);
     }
     __syncthreads();   // the only workgroup barrier
 
     const long long ntiles = (n + tin - 1) / tin;
     const long long GW = (long long)gridDim.x * (NT3 / 64), gw = (long long)blockIdx.x * (NT3 / 64) + wave;
     if (gw >= ntiles) return;
-    const __amdgpu_buffer_rsrc_t rx =
-        __builtin_amdgcn_make_buffer_rsrc((void *)x, (short)0, (int)(n * (long long)sizeof(S)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rh =
-        __builtin_amdgcn_make_buffer_rsrc((void *)hist, (short)0, (int)(L * sizeof(S)), 0x00020000);
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void *)y, (short)0, nout * (int)sizeof(S), 0x00020000);
-    auto ld = [&](__amdgpu_buffer_rsrc_t r, int e) -> S {
-        const unsigned off = e < 0 ? 0xFFFFFFF0u : (unsigned)e * (unsigned)sizeof(S);
-        if constexpr (sizeof(S) == 8)
-            return __builtin_bit_cast(S, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
-        else
-            return __builtin_bit_cast(S, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
-    };
+    const __amdgpu_buffer_rsrc_t rx = lq_buf(x, (int)(n * (long long)sizeof(S)));
+    const __amdgpu_buffer_rsrc_t rh = lq_buf(hist, (int)(L * sizeof(S)));
+    const __amdgpu_buffer_rsrc_t ry = lq_buf(y, nout * (int)sizeof(S));
+    auto ld = [&](__amdgpu_buffer_rsrc_t r, int e) -> S { return lq_buf_ld<S>(r, lq_buf_elem<S>(e)); };
     struct Pre {
         S xa[NXV], xh;
         lqk_rs_entry e;
@@ -443,11 +349,6 @@ __global__ __launch_bounds__(NT3, RS3_BLK) void k_resamp3(lqk_rs_plan pl, unsign
         f.cyc = r.cyc;
         f.skip = r.skip;
     };
-    auto wave_fence = []() {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
     // one tile of loads in flight per wave (a second set measured slower:
     // 82 VGPRs; the CU's other waves hide the latency)
     Pre pa;
@@ -458,7 +359,7 @@ __global__ __launch_bounds__(NT3, RS3_BLK) void k_resamp3(lqk_rs_plan pl, unsign
         const lqk_rs_entry e = pa.e;
         const unsigned long long cyc = pa.cyc;
         const int skip = pa.skip;
-        wave_fence();   // the previous tile's evaluation has read the window
+        lq_wave_fence();   // the previous tile's evaluation has read the window
 #pragma unroll
         for (int u = 0; u < NXV; u++) {
             const int t = lane + 64 * u;
@@ -473,14 +374,7 @@ __global__ __launch_bounds__(NT3, RS3_BLK) void k_resamp3(lqk_rs_plan pl, unsign
         rs_state st;
         const float z = 1.0f - 1.0f / fnpfb;
         if (pl.p2) {
-#pragma clang fp contract(off)
-            for (int i = 0; i < skip; i++) {
-                while (xx < z) {
-                    xx = xx + del;
-                    k++;
-                }
-                xx = xx - 1.0f;
-            }
+            xx = rs_skip_p2(xx, skip, del, z, k);
         } else {
             rs_entry(e, st);
             for (int i = 0; i < skip; i++) k += rs_step(st, del, fnpfb, npfb);
@@ -510,18 +404,7 @@ __global__ __launch_bounds__(NT3, RS3_BLK) void k_resamp3(lqk_rs_plan pl, unsign
         } else {
             for (int r = 0; r < nin; r++) {
                 const int iloc = (int)(ia + r - i0);
-                while ((unsigned)st.b < (unsigned)npfb) {   // unsigned, as resamp.c:254
-                    if (st.st && st.b == npfb - 1) {
-                        st.st = 0;
-                        st.b = npfb;
-                        break;
-                    }
-                    put(iloc, st.st ? st.b : npfb, st.mu);
-                    rs_advance(st, del, fnpfb);
-                    st.st = 1;
-                }
-                st.tau -= 1.0f;
-                st.b = (int)((unsigned)st.b - (unsigned)npfb);
+                rs_input(st, del, fnpfb, npfb, [&](const rs_state &c) { put(iloc, c.st ? c.b : npfb, c.mu); });
             }
         }
         // outputs of the tile: those before the last replaying lane's end
@@ -531,7 +414,7 @@ __global__ __launch_bounds__(NT3, RS3_BLK) void k_resamp3(lqk_rs_plan pl, unsign
         int nr = __builtin_amdgcn_readlane(o, last);
         nr = nr < W3_CAP ? nr : W3_CAP;
         const unsigned ob = (unsigned)(Kb - K0);
-        wave_fence();   // the output list is written
+        lq_wave_fence();   // the output list is written
         auto dot = [&](const S *wv, int bb, float mu) -> S {
             S acc{};
             const float2 *tp = tpl + (bb & 1) * RS + (bb >> 1);
@@ -552,7 +435,7 @@ __global__ __launch_bounds__(NT3, RS3_BLK) void k_resamp3(lqk_rs_plan pl, unsign
                 const uint2 dd = dsc[oo];
                 v = dot(cw + (int)(dd.y & 4095u) + 1, (int)(dd.y >> 12), __uint_as_float(dd.x));
             }
-            rs_store1(ry, oo < nr ? (ob + (unsigned)oo) * (unsigned)sizeof(S) : 0xFFFFFFF0u, v);
+            lq_buf_st<S, RS_STAUX>(ry, oo < nr ? (ob + (unsigned)oo) * (unsigned)sizeof(S) : LQ_BUF_OOR, v);
         }
     }
 }
@@ -572,24 +455,25 @@ rs_route rs_decide(size_t ssz, unsigned long long P, unsigned long long pre, uns
     const bool lds_ok = (size_t)npfb * L * sizeof(float2) <= 64 * 1024;
     if (!(lds_ok && L >= 2 && L <= 32 && (L % 2) == 0)) return rs_route{LQK_RS_ROUTE_GENERIC, NT, 0};
     const bool cst = npfb <= 2 * (RS3_RSC - 1);
-    const size_t lds3 = rs3_lds_bytes(L, ssz, cst ? rs2_rs<RS3_RSC>(npfb) : rs2_rs<0>(npfb));
+    const size_t lds3 = rs3_lds(L, (int)ssz).bytes(cst ? rs2_rs<RS3_RSC>(npfb) : rs2_rs<0>(npfb));
     if (has_taps2 && lds3 <= 80 * 1024 && P < (1ull << 31) && (pre < (1ull << 62) || end < (1ull << 62))) {
         // inputs per wave tile (a multiple of 4): its outputs, at most
         // (tin + 2) r + 2 (tau moves by 1/r per output and by -1 per input
         // within [-1/npfb, 1 + 1/r)), fit the W3_CAP output slots
         const double r = 1.0 / (double)del;
+        auto outs = [r](int t) { return std::ceil((t + 2) * r) + 2; };   // output slots of a t-input tile
         int tin = W3_TIN;
-        while (tin > 4 && std::ceil((tin + 2) * r) + 2 > W3_CAP) tin -= 4;
+        while (tin > 4 && outs(tin) > W3_CAP) tin -= 4;
         // then the tile size with the fewest evaluation passes (64 outputs
         // each, a pass runs only where a lane has an output) per input,
         // counting the tile's fixed cost (window store, replay) as RS3_FIT / 10
         // passes: at r = 1.037 a 256-input tile's 265 outputs take five
         // passes, the fifth for 9 lanes; 244 inputs (253 outputs) take four
-        if (std::ceil((tin + 2) * r) + 2 <= W3_CAP) {
+        if (outs(tin) <= W3_CAP) {
             double best = 1e300;
             int bt = tin;
             for (int t = tin; t >= 4 && t * 4 >= tin * 3; t -= 4) {
-                const double c = (std::ceil((std::ceil((t + 2) * r) + 2) / 64.0) + RS3_FIT / 10.0) / t;
+                const double c = (std::ceil(outs(t) / 64.0) + RS3_FIT / 10.0) / t;
                 if (c < best * (1.0 - 1e-9)) {
                     best = c;
                     bt = t;
@@ -597,7 +481,7 @@ rs_route rs_decide(size_t ssz, unsigned long long P, unsigned long long pre, uns
             }
             tin = bt;
         }
-        if (std::ceil((tin + 2) * r) + 2 <= W3_CAP)   // else (r > ~52): the per-input kernel below
+        if (outs(tin) <= W3_CAP)   // else (r > ~52): the per-input kernel below
             return rs_route{cst ? LQK_RS_ROUTE_R3_CONST : LQK_RS_ROUTE_R3_STRIDE, tin, lds3};
     }
     return rs_route{LQK_RS_ROUTE_RS, RS_R * NT, (size_t)npfb * L * sizeof(float2)};
@@ -613,7 +497,7 @@ void launch_rs(const rs_route &rt, const lqk_rs_plan &pl, unsigned long long g0,
         const int tin = rt.tile;
         const long long ntiles = (n + tin - 1) / tin;
         const long long wgs = (ntiles + NT3 / 64 - 1) / (NT3 / 64);
-        const int blk = lds3 <= 160 * 1024 / RS3_BLK ? RS3_BLK : (int)(160 * 1024 / lds3);
+        const int blk = lds3 <= RS_CU_LDS / RS3_BLK ? RS3_BLK : (int)(RS_CU_LDS / lds3);
         const unsigned nb = lqrt_grid((unsigned long long)wgs, 256u * (unsigned)blk);   // persistent: blk per CU
         if (rt.route == LQK_RS_ROUTE_R3_CONST)
             hipLaunchKernelGGL((k_resamp3<L, S, RS3_RSC>), dim3(nb), dim3(NT3), lds3, st, pl, g0, K0, npfb, del,
@@ -638,31 +522,10 @@ void run_rs(const lqk_rs_plan *pl, unsigned long long g0, unsigned long long K0,
     S *yo = (S *)y;
     const long long nn = (long long)n;
     const rs_route rt = rs_decide(sizeof(S), pl->P, pl->pre, pl->end, (int)npfb, (int)L, del, taps2 != nullptr);
-#define LQ_RS_CASE(LL)                                                                                         \
-    case LL:                                                                                                   \
-        launch_rs<LL, S>(rt, *pl, g0, K0, (int)npfb, del, tp, (const float2 *)taps2, hs, xi, nn, yo, nout, st); \
+    if (rt.route != LQK_RS_ROUTE_GENERIC && rs_taps(L, [&](auto l) {
+            launch_rs<l, S>(rt, *pl, g0, K0, (int)npfb, del, tp, (const float2 *)taps2, hs, xi, nn, yo, nout, st);
+        }))
         return;
-    if (rt.route != LQK_RS_ROUTE_GENERIC) {
-        switch (L) {
-            LQ_RS_CASE(2)
-            LQ_RS_CASE(4)
-            LQ_RS_CASE(6)
-            LQ_RS_CASE(8)
-            LQ_RS_CASE(10)
-            LQ_RS_CASE(12)
-            LQ_RS_CASE(14)
-            LQ_RS_CASE(16)
-            LQ_RS_CASE(18)
-            LQ_RS_CASE(20)
-            LQ_RS_CASE(22)
-            LQ_RS_CASE(24)
-            LQ_RS_CASE(26)
-            LQ_RS_CASE(28)
-            LQ_RS_CASE(30)
-            LQ_RS_CASE(32)
-        }
-    }
-#undef LQ_RS_CASE
     const unsigned nb = (unsigned)((n + NT - 1) / NT);
     hipLaunchKernelGGL((k_resamp_generic<S>), dim3(nb), dim3(NT), 0, st, *pl, g0, K0, (int)npfb, (int)L, del, tp,
                        hs, xi, nn, yo);

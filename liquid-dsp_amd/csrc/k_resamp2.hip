@@ -122,17 +122,29 @@ __global__ __launch_bounds__(NT) void k_resamp2(R2Args a, const C *__restrict__ 
 // in LDS once (each element gathered from history or x a single time instead
 // of once per tap), then each lane evaluates R consecutive calls from a
 // register window of R + 2m - 1 samples.
+// dynamic LDS of the two tiled kernels for windows of W = 2m: the taps, then
+// at byte e1(W) the E_1 span of a tile (CT + W - 1 samples, one of pad), then
+// its E_0 span (CT samples).  The kernels and run_r2 all read it here
+template <typename S, typename C, int R>
+struct r2_lds {
+    static constexpr int CT = NT * R;   // calls per tile
+    __host__ __device__ static constexpr size_t e1(int W) { return (2 * W * sizeof(C) + 15) & ~(size_t)15; }
+    __host__ __device__ static constexpr S *e0(S *e1, int W) { return e1 + CT + W; }
+    __host__ __device__ static constexpr size_t bytes(int W) { return e1(W) + (size_t)(2 * CT + W) * sizeof(S); }
+};
+
 template <typename S, typename C, int R>
 __global__ __launch_bounds__(NT) void k_resamp2_tiled(R2Args a, const C *__restrict__ taps,
                                                       const S *__restrict__ hist0, const S *__restrict__ hist1,
                                                       const S *__restrict__ x, S *__restrict__ y0)
 {
-    constexpr int CT = NT * R;                    // calls per tile
+    typedef r2_lds<S, C, R> LY;
+    constexpr int CT = LY::CT;
     extern __shared__ __attribute__((aligned(16))) unsigned char r2_smem[];
     const int m = a.m, W = 2 * m;
     C *th = reinterpret_cast<C *>(r2_smem);
-    S *e1 = reinterpret_cast<S *>(r2_smem + ((2 * W * sizeof(C) + 15) & ~15));   // E_1[i0+1 ...], CT + W - 1
-    S *e0 = e1 + CT + W;                                                       // E_0[W + i0 - m ...], CT
+    S *e1 = reinterpret_cast<S *>(r2_smem + LY::e1(W));   // E_1[i0+1 ...], CT + W - 1
+    S *e0 = LY::e0(e1, W);                                // E_0[W + i0 - m ...], CT
     const long long i0 = (long long)blockIdx.x * CT;
     for (int j = threadIdx.x; j < W; j += NT) th[j] = taps[j];
     for (int u = threadIdx.x; u < CT + W - 1; u += NT) {
@@ -180,11 +192,7 @@ __global__ __launch_bounds__(NT) void k_resamp2_tiled(R2Args a, const C *__restr
 template <typename S>
 __device__ __forceinline__ S r2_ldb(__amdgpu_buffer_rsrc_t r, long long idx)
 {
-    const unsigned off = (unsigned)(idx * (long long)sizeof(S));   // idx < 0: out of range, 0
-    if constexpr (sizeof(S) == 8)
-        return __builtin_bit_cast(S, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
-    else
-        return __builtin_bit_cast(S, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
+    return lq_buf_ld<S>(r, (unsigned)(idx * (long long)sizeof(S)));   // idx < 0: out of range, 0
 }
 
 template <typename S, typename C, int R, int MODE>
@@ -193,19 +201,19 @@ __global__ __launch_bounds__(NT) void k_resamp2_tiled_b(R2Args a, const C *__res
                                                         const S *__restrict__ x, S *__restrict__ y0)
 {
     const bool al16 = ((unsigned long long)y0 & 15) == 0;
-    constexpr int CT = NT * R;
+    typedef r2_lds<S, C, R> LY;
+    constexpr int CT = LY::CT;
     constexpr int NU = (CT + 32 - 1 + NT - 1) / NT;   // staging slots per lane (2m <= 32)
     extern __shared__ __attribute__((aligned(16))) unsigned char r2_smem[];
     const int m = a.m, W = 2 * m;
     C *th = reinterpret_cast<C *>(r2_smem);
-    S *e1 = reinterpret_cast<S *>(r2_smem + ((2 * W * sizeof(C) + 15) & ~15));
-    S *e0 = e1 + CT + W;
+    S *e1 = reinterpret_cast<S *>(r2_smem + LY::e1(W));
+    S *e0 = LY::e0(e1, W);
     const long long i0 = (long long)blockIdx.x * CT;
     const int ES = (int)sizeof(S);
     const long long nx = MODE == LQK_R2_INTERP ? a.n : 2 * a.n;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)x, (short)0, (int)(nx * ES), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rh0 = __builtin_amdgcn_make_buffer_rsrc((void *)hist0, (short)0, W * ES, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rh1 = __builtin_amdgcn_make_buffer_rsrc((void *)hist1, (short)0, W * ES, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = lq_buf(x, (int)(nx * ES));
+    const __amdgpu_buffer_rsrc_t rh0 = lq_buf(hist0, W * ES), rh1 = lq_buf(hist1, W * ES);
     // E_p[k]: history part (k < W) + push part c = k - W (zero where out of range)
     auto E = [&](int p, long long k, S &h, S &u, S &v) {
         const long long c = k - W;
@@ -337,19 +345,14 @@ void run_r2(const R2Args &a, const void *taps, const void *h0, const void *h1, v
         hipLaunchKernelGGL((k_resamp2<S, C>), dim3(grid), dim3(NT), (size_t)2 * a.m * sizeof(C), st, a,
                            (const C *)taps, (const S *)h0, (const S *)h1, (const S *)x, (S *)y0, (S *)y1);
     } else {
-        constexpr int R = 4, CT = NT * R;
-        const size_t lds = ((2 * 2 * a.m * sizeof(C) + 15) & ~(size_t)15) + (size_t)(2 * CT + 2 * a.m) * sizeof(S);
+        constexpr int R = 4, CT = r2_lds<S, C, R>::CT;
+        const size_t lds = r2_lds<S, C, R>::bytes(2 * a.m);
         const unsigned grid = (unsigned)((a.n + CT - 1) / CT);
         if (route == LQK_R2_ROUTE_TILED_B) {
-            switch (a.mode) {
-#define LQ_R2B(MD)                                                                                         \
-    case MD:                                                                                               \
-        hipLaunchKernelGGL((k_resamp2_tiled_b<S, C, R, MD>), dim3(grid), dim3(NT), lds, st, a, (const C *)taps, \
-                           (const S *)h0, (const S *)h1, (const S *)x, (S *)y0);                           \
-        break;
-                LQ_R2B(LQK_R2_DECIM) LQ_R2B(LQK_R2_ANALYZER) LQ_R2B(LQK_R2_INTERP) LQ_R2B(LQK_R2_SYNTHESIZER)
-#undef LQ_R2B
-            }
+            lq_switch<LQK_R2_DECIM, LQK_R2_ANALYZER, LQK_R2_INTERP, LQK_R2_SYNTHESIZER>(a.mode, [&](auto md) {
+                hipLaunchKernelGGL((k_resamp2_tiled_b<S, C, R, md>), dim3(grid), dim3(NT), lds, st, a, (const C *)taps,
+                                   (const S *)h0, (const S *)h1, (const S *)x, (S *)y0);
+            });
         } else {
             hipLaunchKernelGGL((k_resamp2_tiled<S, C, R>), dim3(grid), dim3(NT), lds, st, a, (const C *)taps,
                                (const S *)h0, (const S *)h1, (const S *)x, (S *)y0);

@@ -68,6 +68,7 @@
 
 #include "lq_device.h"
 #include "lq_kernels.h"
+#include "lq_resamp.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -77,7 +78,7 @@ namespace {
 constexpr int NT4 = 256;       // 4 waves per workgroup; each wave owns its tiles end to end
 constexpr int TOUT = 256;      // outputs per wave tile (4 per lane)
 // tap reads per group in flight: the next group is issued before the current
-// one is consumed (the volatile reads, one at a time, exposed the LDS latency
+// one is consumed (the lds_rd reads, one at a time, exposed the LDS latency
 // per tap: 0.127 -> 0.124 ms at config 5, profiles/r05_ab_experiments.txt)
 // (1 < r <= 2, L <= 16 with the two windows in flight; elsewhere the
 // grouping's register pressure spilled, and a pass issues its reads one by one)
@@ -112,21 +113,23 @@ constexpr int rs4_pad() { return UP ? 2 : (DN ? 6 : 3); }   // zero tap rows eit
 template <int L, bool UP, bool DN = false>
 constexpr int rs4_rows() { return L + 1 + 2 * rs4_pad<UP, DN>(); }
 
-// one 8-byte LDS read, volatile: issued as its own ds_read_b64 (2 LDS cycles
-// per wave instruction), never paired into a ds_read2_b64 (8 cycles)
-__device__ __forceinline__ float2 lds_rd8(const float2 *p)
-{
-    typedef const volatile unsigned long long __attribute__((address_space(3))) *lp;
-    const unsigned long long u = *(lp)(p);
-    return __builtin_bit_cast(float2, u);
-}
+// outputs a tile of the fused stage (semi-length hm) recomputes from the tile
+// before it, a multiple of 4 (see k_resamp4), and the outputs a tile keeps
+constexpr int rs4_halo(int hm) { return hm ? ((2 * hm - 1 + 3) & ~3) : 0; }
+constexpr int rs4_ts(int hm) { return TOUT - rs4_halo(hm); }
 
-__device__ __forceinline__ void wave_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// dynamic LDS of k_resamp4: the tap table, rows of rs = npfb + 1 pairs (== 1
+// mod 32 for npfb >= 32), then per wave the transposed window.  The kernel
+// and launch_rs4_c both read it here
+template <int L, bool UP, bool DN, int HM>
+struct rs4_lds {
+    static constexpr int HALO = rs4_halo(HM), TS = rs4_ts(HM);
+    static constexpr int NR = rs4_rows<L, UP, DN>(), N4 = rs4_n4<UP, DN>();
+    static constexpr int WIN = 4 * N4;   // float2 slots of a wave's window
+    __host__ __device__ static constexpr int rs(int npfb) { return npfb + 1; }
+    __host__ __device__ static constexpr int table(int rs) { return (NR * rs * 8 + 15) & ~15; }   // bytes
+    __host__ __device__ static constexpr size_t bytes(int rs) { return (size_t)table(rs) + (size_t)(NT4 / 64) * WIN * 8; }
+};
 
 template <int L, int NPC, bool UP, int HM, bool R4 = false, bool DN = false>
 __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp4(lqk_rs4_plan pl, unsigned long long g0,
@@ -143,14 +146,12 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
     // 256 resampler outputs starting HALO >= 2 HM - 1 outputs early, so the
     // stage's window for the tile's TS = 256 - HALO new outputs is complete
     // (the HALO outputs are the previous tile's, recomputed: 4.7 % at HM = 6)
+    typedef rs4_lds<L, UP, DN, HM> LY;
     constexpr int HW = 2 * HM;
-    constexpr int HALO = HM ? ((HW - 1 + 3) & ~3) : 0;
-    constexpr int TS = TOUT - HALO;
+    constexpr int HALO = LY::HALO, TS = LY::TS;
     static_assert(HM == 0 || (UP && HALO >= HW && HALO < 64), "fused half-band stage shape");
-    constexpr int NR = rs4_rows<L, UP, DN>();
+    constexpr int NR = LY::NR, N4 = LY::N4;
     constexpr int PAD = rs4_pad<UP, DN>();
-    constexpr int N4 = rs4_n4<UP, DN>();
-    constexpr int LP = (L + 3) & ~1;                 // pair stride of taps2 (host layout)
     constexpr int TSW = rs4_tsw<L, UP, DN>();
     constexpr int NXV = (TSW + 63) / 64;             // window samples per lane
     constexpr int NW = UP ? L + 4 : (DN ? L + 13 : L + 7);   // register window per lane
@@ -159,17 +160,13 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
     constexpr int RG = rs4_rg<L, UP, HM>();
     static_assert(TSW <= 4 * N4, "window exceeds the transposed layout");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int RS = NPC ? NPC + 1 : npfb + 1;         // table row stride (== 1 mod 32 for npfb >= 32)
+    const int RS = LY::rs(NPC ? NPC : npfb);         // table row stride
     float2 *tt = reinterpret_cast<float2 *>(smem);   // tt[(p + PAD) RS + b] = (h_b[p], h_{b+1}[p] - h_b[p])
-    const int tbytes = (NR * RS * 8 + 15) & ~15;
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     for (int e = tid; e < NR * RS; e += NT4) {
         const int rr = e / RS, b = e - rr * RS, p = rr - PAD;
         float2 v = make_float2(0.0f, 0.0f);
-        if (p >= 0 && p <= L && b <= npfb) {
-            const float2 t = taps2[b * LP + p];
-            v = make_float2(t.x, t.y - t.x);
-        }
+        if (p >= 0 && p <= L && b <= npfb) v = rs_pair(taps2, b * rs_lp<L>() + p);
         tt[e] = v;
     }
     __syncthreads();   // the only workgroup barrier
@@ -177,18 +174,13 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
     const int ntiles = (nout + TS - 1) / TS;
     const int GW = (int)gridDim.x * (NT4 / 64), gw = (int)blockIdx.x * (NT4 / 64) + wave;
     if (gw >= ntiles) return;
-    float2 *win = reinterpret_cast<float2 *>(smem + tbytes) + wave * (4 * N4);
+    float2 *win = reinterpret_cast<float2 *>(smem + LY::table(RS)) + wave * LY::WIN;
 
-    const __amdgpu_buffer_rsrc_t ry =
-        __builtin_amdgcn_make_buffer_rsrc((void *)y, (short)0, nout * (HM ? 16 : 8), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rt =
-        __builtin_amdgcn_make_buffer_rsrc((void *)pl.tab, (short)0, (int)(pl.ntab * 8), 0x00020000);
-    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    const __amdgpu_buffer_rsrc_t ry = lq_buf(y, nout * (HM ? 16 : 8));
+    const __amdgpu_buffer_rsrc_t rt = lq_buf(pl.tab, (int)(pl.ntab * 8));
     typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-    auto ld8 = [&](__amdgpu_buffer_rsrc_t r, int e) -> float2 {
-        const unsigned off = e < 0 ? 0xFFFFFFF0u : (unsigned)e * 8u;
-        return __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
-    };
+    auto pk4 = [](v2f a, v2f b) { return __builtin_bit_cast(u32x4, __builtin_shufflevector(a, b, 0, 1, 2, 3)); };
+    auto ld8 = [&](__amdgpu_buffer_rsrc_t r, int e) -> float2 { return lq_buf_ld<float2>(r, lq_buf_elem<float2>(e)); };
 
     // Table entries.  The table holds the state at outputs 0, 4, 8, ... below
     // pre (npre entries), then at pre, pre + 4, ... within one period of QT
@@ -274,8 +266,7 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
         const bool live = tile < ntiles;
         if (ws >= 0) {   // (wave-uniform) the usual case: a descriptor based at x[ws], constant lane offsets
             const long long rem = (long long)n - ws;
-            const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(
-                (void *)(x + ws), (short)0, live && rem > 0 ? (int)(rem * 8) : 0, 0x00020000);
+            const __amdgpu_buffer_rsrc_t r = lq_buf(x + ws, live && rem > 0 ? (int)(rem * 8) : 0);
 #pragma unroll
             for (int u = 0; u < NXV; u++)
                 w.v[u] = ld8(r, lane + 64 * u < TSW ? lane + 64 * u : -1);
@@ -369,14 +360,14 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
         // lane window W[q] = x[ia - L + q] = window sample a + q
         int a = ia - i_e;
         a = a < 0 ? 0 : (a > AMAX ? AMAX : a);   // lanes past the call's outputs
-        wave_fence();   // the window is in LDS
+        lq_wave_fence();   // the window is in LDS
         v2f W[NW];
         {
             const float2 *wb[4];
 #pragma unroll
             for (int c = 0; c < 4; c++) wb[c] = win + ((a + c) & 3) * N4 + ((a + c) >> 2);
 #pragma unroll
-            for (int q = 0; q < NW; q++) W[q] = pk(lds_rd8(wb[q & 3] + (q >> 2)));
+            for (int q = 0; q < NW; q++) W[q] = pk(lds_rd(wb[q & 3] + (q >> 2)));
         }
         // four outputs: pass s over q in [lo, hi] (UP: d_0 = 0, d_1 <= 1,
         // 1 <= d_2 <= 2, 1 <= d_3 <= 3; R4: 0 <= d_s <= {0, 1, 1, 2}; !UP:
@@ -392,11 +383,11 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
             v2f sacc = {0.0f, 0.0f};
             // tap reads in groups of RG, the next group issued before the
             // current one is consumed (one read at a time exposed the LDS
-            // latency per tap: the volatile reads are never hoisted)
+            // latency per tap: the lds_rd reads are never hoisted)
             if constexpr (RG == 1) {
 #pragma unroll
                 for (int q = lo; q <= hi; q++) {
-                    const float2 t = lds_rd8(tb + q * RS);
+                    const float2 t = lds_rd(tb + q * RS);
                     const float cf = __builtin_fmaf(m, t.y, t.x);
                     sacc = v2f{cf, cf} * W[q] + sacc;
                 }
@@ -404,13 +395,13 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
             float2 tg[2][RG];
 #pragma unroll
             for (int g = 0; g < RG; g++)
-                if (lo + g <= hi) tg[0][g] = lds_rd8(tb + (lo + g) * RS);
+                if (lo + g <= hi) tg[0][g] = lds_rd(tb + (lo + g) * RS);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int q0 = lo, c = 0; q0 <= hi; q0 += RG, c ^= 1) {
 #pragma unroll
                 for (int g = 0; g < RG; g++)
-                    if (q0 + RG + g <= hi) tg[c ^ 1][g] = lds_rd8(tb + (q0 + RG + g) * RS);
+                    if (q0 + RG + g <= hi) tg[c ^ 1][g] = lds_rd(tb + (q0 + RG + g) * RS);
                 __builtin_amdgcn_sched_barrier(0);   // the group's reads stay ahead of the arithmetic
 #pragma unroll
                 for (int g = 0; g < RG; g++) {
@@ -455,13 +446,13 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
             // then evaluates the stage at t = j + 64 s, so its two outputs per
             // t leave as one 16-byte store and each store instruction writes
             // 1 KB contiguous
-            wave_fence();
+            lq_wave_fence();
             {
                 float4 *u4 = reinterpret_cast<float4 *>(win);
                 u4[2 * lane] = make_float4(acc[0].x, acc[0].y, acc[1].x, acc[1].y);
                 u4[2 * lane + 1] = make_float4(acc[2].x, acc[2].y, acc[3].x, acc[3].y);
             }
-            wave_fence();
+            lq_wave_fence();
             // then per t: the odd-tap dot product and the delay sample, and
             // the two outputs 2k, 2k+1 of resampler output k = tile TS + t -
             // HALO as one 16-byte store (the halo's t < HALO store nothing)
@@ -470,8 +461,8 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
                 const float2 *ub = win + lane + 64 * s - (HW - 1);   // u[t - (HW-1) + q]
                 v2f a = {0.0f, 0.0f}, d = {0.0f, 0.0f};
 #pragma unroll
-                for (int j = 0; j < HW; j++) {   // the odd-tap branch, in the order of k_resamp2
-                    const v2f v = pk(lds_rd8(ub + j));
+                for (int j = 0; j < HW; j++) {   // the odd-tap branch, in the order of k_resamp2_tiled_b
+                    const v2f v = pk(lds_rd(ub + j));
                     const float h = hb.h1[j];
                     a = v2f{h, h} * v + a;
                     if (j == HM - 1) d = v;   // the delay branch u[t - m]
@@ -480,35 +471,21 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
                 const int t = lane + 64 * s, k = tile * TS + t - HALO;
                 if (t >= HALO && k < nout) {
                     if (smode) {
-                        u32x4 v;
-                        v.x = __float_as_uint(d.x);
-                        v.y = __float_as_uint(d.y);
-                        v.z = __float_as_uint(a.x);
-                        v.w = __float_as_uint(a.y);
-                        __builtin_amdgcn_raw_buffer_store_b128(v, ry, (unsigned)k * 16u, 0, 2);
+                        lq_buf_st<u32x4, 2>(ry, (unsigned)k * 16u, pk4(d, a));
                     } else {
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, d), ry, (unsigned)k * 16u, 0, 2);
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, a), ry,
-                                                              (unsigned)k * 16u + 8u, 0, 2);
+                        lq_buf_st<v2f, 2>(ry, (unsigned)k * 16u, d);
+                        lq_buf_st<v2f, 2>(ry, (unsigned)k * 16u + 8u, a);
                     }
                 }
             }
         }
         // the next tile's window into LDS (this tile's window reads are done)
-        wave_fence();
+        lq_wave_fence();
         put_window(wbuf);
         const int ws2 = __builtin_amdgcn_readfirstlane(ent_i(PF == 2 ? e3 : enn)) - L;   // the window to fetch
         if constexpr (HM == 0) {
             // stores: outputs tile*256 + 4 lane + s, two 16-byte stores per lane
-            u32x4 s01, s23;
-            s01.x = __float_as_uint(acc[0].x);
-            s01.y = __float_as_uint(acc[0].y);
-            s01.z = __float_as_uint(acc[1].x);
-            s01.w = __float_as_uint(acc[1].y);
-            s23.x = __float_as_uint(acc[2].x);
-            s23.y = __float_as_uint(acc[2].y);
-            s23.z = __float_as_uint(acc[3].x);
-            s23.w = __float_as_uint(acc[3].y);
+            const u32x4 s01 = pk4(acc[0], acc[1]), s23 = pk4(acc[2], acc[3]);
             if (smode == 2 && tile * TOUT + TOUT <= nout) {
                 // whole 128-byte lines per store instruction: lanes j and j ^ 4
                 // (quads A, B of an 8-lane group; outputs 32 g .. 32 g + 31)
@@ -523,16 +500,15 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
                 rcv.z = (unsigned)__builtin_amdgcn_ds_swizzle((int)snd.z, 0x101F);
                 rcv.w = (unsigned)__builtin_amdgcn_ds_swizzle((int)snd.w, 0x101F);
                 const unsigned o1 = (unsigned)(tile * TOUT + 32 * (lane >> 3) + 4 * (lane & 3) + 2 * b2) * 8u;
-                __builtin_amdgcn_raw_buffer_store_b128(b2 ? rcv : s01, ry, o1, 0, 2);
-                __builtin_amdgcn_raw_buffer_store_b128(b2 ? s23 : rcv, ry, o1 + 128u, 0, 2);
+                lq_buf_st<u32x4, 2>(ry, o1, b2 ? rcv : s01);
+                lq_buf_st<u32x4, 2>(ry, o1 + 128u, b2 ? s23 : rcv);
             } else if (ko + 4 <= nout && smode) {
-                __builtin_amdgcn_raw_buffer_store_b128(s01, ry, (unsigned)ko * 8u, 0, 2);
-                __builtin_amdgcn_raw_buffer_store_b128(s23, ry, (unsigned)ko * 8u + 16u, 0, 2);
+                lq_buf_st<u32x4, 2>(ry, (unsigned)ko * 8u, s01);
+                lq_buf_st<u32x4, 2>(ry, (unsigned)ko * 8u + 16u, s23);
             } else if (ko < nout) {   // the call's ragged end (one lane of one wave), or y not 16-byte aligned
                 for (int s = 0; s < 4; s++)
                     if (ko + s < nout)
-                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, acc[s]), ry,
-                                                              (unsigned)(ko + s) * 8u, 0, 2);
+                        lq_buf_st<v2f, 2>(ry, (unsigned)(ko + s) * 8u, acc[s]);
             }
         }
         fetch(tile + (PF + 1) * GW, ws2, wbuf);
@@ -555,9 +531,6 @@ __global__ __launch_bounds__(NT4, (HM ? 4 : rs4_blk<L, UP, DN>())) void k_resamp
     }
 }
 
-// outputs a wave tile keeps: the fused stage's tiles overlap by its halo
-constexpr int rs4_ts(int hm) { return TOUT - (hm ? ((2 * hm - 1 + 3) & ~3) : 0); }
-
 template <int L, bool UP, int HM, bool R4 = false, bool DN = false>
 void launch_rs4_c(const lqk_rs4_plan &pl, unsigned long long g0, unsigned long long K0, int npfb, float del,
                   const float2 *taps2, const float2 *hist, const float2 *x, int n, float2 *y, int nout,
@@ -568,14 +541,13 @@ void launch_rs4_c(const lqk_rs4_plan &pl, unsigned long long g0, unsigned long l
     // ragged last tile): 0.1117-0.1120 -> 0.1099-0.1112 ms at config 5
     // (profiles/r06_ab_experiments.txt, r06d); 0: y only 8-byte aligned
     const int smode = ((unsigned long long)y & 15) ? 0 : 2;
-    const int RS = npfb + 1;
-    const size_t lds =
-        (size_t)((rs4_rows<L, UP, DN>() * RS * 8 + 15) & ~15) + (size_t)(NT4 / 64) * 4 * rs4_n4<UP, DN>() * 8;
-    constexpr int TS = rs4_ts(HM);
+    typedef rs4_lds<L, UP, DN, HM> LY;
+    const size_t lds = LY::bytes(LY::rs(npfb));
+    constexpr int TS = LY::TS;
     const int ntiles = (nout + TS - 1) / TS;
     const int wgs = (ntiles + NT4 / 64 - 1) / (NT4 / 64);
     constexpr int B = HM ? 4 : rs4_blk<L, UP, DN>();   // the fused stage's window needs the VGPRs of a fifth
-    const int blk = lds * B <= 160 * 1024 ? B : (int)(160 * 1024 / lds);
+    const int blk = lds * B <= RS_CU_LDS ? B : (int)(RS_CU_LDS / lds);
     const int nb = (int)lqrt_grid((unsigned long long)wgs, 256u * (unsigned)blk);   // persistent: blk per CU
     if (npfb == 64)
         hipLaunchKernelGGL((k_resamp4<L, 64, UP, HM, R4, DN>), dim3(nb), dim3(NT4), lds, st, pl, g0, K0, npfb, del,
@@ -616,6 +588,12 @@ void launch_rs4(const lqk_rs4_plan &pl, unsigned long long g0, unsigned long lon
     }
 }
 
+[[noreturn]] void rs4_outside(unsigned int npfb, unsigned int L, unsigned long long n)
+{
+    fprintf(stderr, "error: liquid-mi355x: resamp4 launch outside its shape (npfb %u, L %u, %llu inputs)\n", npfb, L, n);
+    exit(1);
+}
+
 } // namespace
 
 extern "C" int lqk_resamp4_supported(unsigned int npfb, unsigned int L)
@@ -648,48 +626,21 @@ extern "C" void lqk_resamp4(const lqk_rs4_plan *pl, unsigned long long g0, unsig
     const lqk_hist_job hj = job ? *job : lqk_hist_job{nullptr, nullptr, 0ull, nullptr, 0u};
     if (!lqk_resamp4_supported(npfb, L) || n > LQK_RS_MAXN || nout * (hb ? 16ull : 8ull) >= (1ull << 31) ||
         pl->ntab * 8ull >= (1ull << 31) || !(pl->pre == ~0ull || (pl->QT >= TOUT && pl->npre == (pl->pre + 3) / 4)) ||
-        (hb && !lqk_resamp4_hb_supported(npfb, L, del, hb->m))) {
-        fprintf(stderr, "error: liquid-mi355x: resamp4 launch outside its shape (npfb %u, L %u, %llu inputs)\n", npfb, L, n);
-        exit(1);
-    }
+        (hb && !lqk_resamp4_hb_supported(npfb, L, del, hb->m)))
+        rs4_outside(npfb, L, n);
     hipStream_t st = (hipStream_t)stream;
     const float2 *t2 = (const float2 *)taps2, *h = (const float2 *)hist, *xi = (const float2 *)x;
     float2 *yo = (float2 *)y;
     if (hb) {
-        switch (hb->m) {
-#define LQ_RS4_HB(MM)                                                                                   \
-    case MM:                                                                                            \
-        launch_rs4_c<14, true, MM>(*pl, g0, K0, 64, del, t2, h, xi, (int)n, yo, (int)nout, *hb, hj, st); \
-        break;
-            LQ_RS4_HB(3) LQ_RS4_HB(4) LQ_RS4_HB(5) LQ_RS4_HB(6) LQ_RS4_HB(7)
-            LQ_RS4_HB(8) LQ_RS4_HB(9) LQ_RS4_HB(10) LQ_RS4_HB(11) LQ_RS4_HB(12)
-#undef LQ_RS4_HB
-        }
-        LQ_CHECK_LAUNCH();
-        return;
+        // the fused stage's semi-lengths 3 .. LQK_RS4_HB_MAXM
+        if (!lq_switch<3, 4, 5, 6, 7, 8, 9, 10, 11, 12>(hb->m, [&](auto m) {
+                launch_rs4_c<14, true, m>(*pl, g0, K0, 64, del, t2, h, xi, (int)n, yo, (int)nout, *hb, hj, st);
+            }))
+            rs4_outside(npfb, L, n);
+    } else if (!rs_taps(L, [&](auto l) {
+                   launch_rs4<l>(*pl, g0, K0, (int)npfb, del, t2, h, xi, (int)n, yo, (int)nout, hj, st);
+               })) {
+        rs4_outside(npfb, L, n);
     }
-#define LQ_RS4_CASE(LL)                                                                                 \
-    case LL:                                                                                            \
-        launch_rs4<LL>(*pl, g0, K0, (int)npfb, del, t2, h, xi, (int)n, yo, (int)nout, hj, st);          \
-        break;
-    switch (L) {
-        LQ_RS4_CASE(2)
-        LQ_RS4_CASE(4)
-        LQ_RS4_CASE(6)
-        LQ_RS4_CASE(8)
-        LQ_RS4_CASE(10)
-        LQ_RS4_CASE(12)
-        LQ_RS4_CASE(14)
-        LQ_RS4_CASE(16)
-        LQ_RS4_CASE(18)
-        LQ_RS4_CASE(20)
-        LQ_RS4_CASE(22)
-        LQ_RS4_CASE(24)
-        LQ_RS4_CASE(26)
-        LQ_RS4_CASE(28)
-        LQ_RS4_CASE(30)
-        LQ_RS4_CASE(32)
-    }
-#undef LQ_RS4_CASE
     LQ_CHECK_LAUNCH();
 }

@@ -271,19 +271,19 @@ __global__ __launch_bounds__(NT, 3) void k_spg_fused1024(const S *__restrict__ h
         else pk_dft16<+1>(v);
 #pragma unroll
         for (int k = 1; k < 16; k++) v[k] = pk_cmul(v[k], TR ? T1[k - 1] : pk(tw1[k * 64 + lane]));
-        f1k_wave_fence();
+        lq_wave_fence();
 #pragma unroll
         for (int k = 0; k < 16; k++) B[k * 68 + lane] = unpk(v[k]);
-        f1k_wave_fence();
+        lq_wave_fence();
 #pragma unroll
         for (int a = 0; a < 16; a++) v[a] = pk(B[k1 * 68 + 4 * a + bq]);
         pk_dft16<+1>(v);
 #pragma unroll
         for (int r = 1; r < 16; r++) v[r] = pk_cmul(v[r], pk(tw2[r * 4 + bq]));
-        f1k_wave_fence();
+        lq_wave_fence();
 #pragma unroll
         for (int r = 0; r < 16; r++) B[k1 + 16 * r + 260 * bq] = unpk(v[r]);
-        f1k_wave_fence();
+        lq_wave_fence();
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             v4f c[4];
@@ -303,7 +303,7 @@ __global__ __launch_bounds__(NT, 3) void k_spg_fused1024(const S *__restrict__ h
                 qb = accum ? (1.0f - alpha) * qb + alpha * pb : qb + pb;
             }
         }
-        f1k_wave_fence();   // B is rewritten by the next transform
+        lq_wave_fence();   // B is rewritten by the next transform
     }
 #pragma unroll
     for (int u = 0; u < 2; u++)

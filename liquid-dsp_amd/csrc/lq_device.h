@@ -48,6 +48,49 @@ __device__ __forceinline__ void lq_lds_sync()
     asm volatile("" ::: "memory");
 }
 
+// Hand-off through LDS within one wave (a wave that owns its tile end to
+// end): orders the wave's LDS accesses either side, no workgroup barrier.
+__device__ __forceinline__ void lq_wave_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Range-checked view of `bytes` bytes from p (raw buffer, 32-bit byte
+// offsets): a load at an offset past the view returns 0, a store there is
+// dropped.  LQ_BUF_OOR is past every view (views are < 2^31 bytes), for
+// lanes that have nothing to load or store.
+constexpr unsigned LQ_BUF_OOR = 0xFFFFFFF0u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t lq_buf(const void *p, int bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc((void *)p, (short)0, bytes, 0x00020000);
+}
+// byte offset of element e of T; e < 0: out of range
+template <typename T>
+__device__ __forceinline__ unsigned lq_buf_elem(int e)
+{
+    return e < 0 ? LQ_BUF_OOR : (unsigned)e * (unsigned)sizeof(T);
+}
+// one element of 4, 8 or 16 bytes at byte offset off; AUX: the store's cache
+// policy bits (2: non-temporal)
+template <typename T>
+__device__ __forceinline__ T lq_buf_ld(__amdgpu_buffer_rsrc_t r, unsigned off)
+{
+    if constexpr (sizeof(T) == 16) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
+    else if constexpr (sizeof(T) == 8) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
+    else return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0));
+}
+template <typename T, int AUX = 0>
+__device__ __forceinline__ void lq_buf_st(__amdgpu_buffer_rsrc_t r, unsigned off, T v)
+{
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    if constexpr (sizeof(T) == 16) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, AUX);
+    else if constexpr (sizeof(T) == 8) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), r, off, 0, AUX);
+    else __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, off, 0, AUX);
+}
+
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ float2 cmul(float2 a, float2 b)

@@ -9,13 +9,6 @@
 
 #include "lq_device.h"
 
-__device__ __forceinline__ void f1k_wave_fence()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // tw1[k1*64 + t] = W_1024^{DIR t k1}, tw2[r*4 + b] = W_64^{DIR b r} (tw4096: exp(-2 pi i e/4096))
 template <int DIR>
 __device__ __forceinline__ void f1k_tables(float2 *tw1, float2 *tw2, const float2 *__restrict__ tw4096)
@@ -48,10 +41,10 @@ __device__ __forceinline__ void fft1024_wave(float2 (&v)[16], float2 *B, const f
     pk_dft16<DIR>(p);
 #pragma unroll
     for (int k1 = 1; k1 < 16; k1++) p[k1] = pk_cmul(p[k1], pk(tw1[k1 * 64 + lane]));
-    f1k_wave_fence();
+    lq_wave_fence();
 #pragma unroll
     for (int k1 = 0; k1 < 16; k1++) B[k1 * 68 + lane] = unpk(p[k1]);
-    f1k_wave_fence();
+    lq_wave_fence();
     const int k1 = lane >> 2, bq = lane & 3;
 #pragma unroll
     for (int a = 0; a < 16; a++) p[a] = pk(B[k1 * 68 + 4 * a + bq]);
@@ -59,10 +52,10 @@ __device__ __forceinline__ void fft1024_wave(float2 (&v)[16], float2 *B, const f
 #pragma unroll
     for (int r = 1; r < 16; r++) p[r] = pk_cmul(p[r], pk(tw2[r * 4 + bq]));
     // C[k1][bq][r] at k1 + 16 r + 260 bq (conflict-free b64 writes, b128 reads)
-    f1k_wave_fence();
+    lq_wave_fence();
 #pragma unroll
     for (int r = 0; r < 16; r++) B[k1 + 16 * r + 260 * bq] = unpk(p[r]);
-    f1k_wave_fence();
+    lq_wave_fence();
     typedef float v4f __attribute__((ext_vector_type(4)));
     // lane (t2, p2): bins k1 = 2 p2 + {0, 1}, r = t2 + 8u
     const int t2 = lane >> 3, p2 = lane & 7;
@@ -72,7 +65,7 @@ __device__ __forceinline__ void fft1024_wave(float2 (&v)[16], float2 *B, const f
 #pragma unroll
         for (int q = 0; q < 4; q++)
             c[u][q] = *reinterpret_cast<const v4f *>(B + 2 * p2 + 16 * (t2 + 8 * u) + 260 * q);
-    f1k_wave_fence();
+    lq_wave_fence();
 #pragma unroll
     for (int u = 0; u < 2; u++) {
         v2f e0[4] = {c[u][0].xy, c[u][1].xy, c[u][2].xy, c[u][3].xy};
@@ -90,7 +83,7 @@ __device__ __forceinline__ void fft1024_wave(float2 (&v)[16], float2 *B, const f
             *reinterpret_cast<v4f *>(B + 2 * p2 + 16 * (t2 + 8 * u) + 260 * sidx) = val;
         }
     }
-    f1k_wave_fence();
+    lq_wave_fence();
 }
 
 // fft1024_wave with the first twiddle W_1024^{DIR lane k1} formed in
@@ -104,20 +97,20 @@ __device__ __forceinline__ void fft1024_wave_rt(float2 (&v)[16], float2 *B, floa
     dft16<DIR>(v);
     twiddle16v<DIR>(v, a1, a4);
     v2f p[16];
-    f1k_wave_fence();
+    lq_wave_fence();
 #pragma unroll
     for (int k1 = 0; k1 < 16; k1++) B[k1 * 68 + lane] = v[k1];
-    f1k_wave_fence();
+    lq_wave_fence();
     const int k1 = lane >> 2, bq = lane & 3;
 #pragma unroll
     for (int a = 0; a < 16; a++) p[a] = pk(B[k1 * 68 + 4 * a + bq]);
     pk_dft16<DIR>(p);
 #pragma unroll
     for (int r = 1; r < 16; r++) p[r] = pk_cmul(p[r], pk(tw2[r * 4 + bq]));
-    f1k_wave_fence();
+    lq_wave_fence();
 #pragma unroll
     for (int r = 0; r < 16; r++) B[k1 + 16 * r + 260 * bq] = unpk(p[r]);
-    f1k_wave_fence();
+    lq_wave_fence();
     typedef float v4f __attribute__((ext_vector_type(4)));
     const int t2 = lane >> 3, p2 = lane & 7;
     v4f c[2][4];
@@ -126,7 +119,7 @@ __device__ __forceinline__ void fft1024_wave_rt(float2 (&v)[16], float2 *B, floa
 #pragma unroll
         for (int q = 0; q < 4; q++)
             c[u][q] = *reinterpret_cast<const v4f *>(B + 2 * p2 + 16 * (t2 + 8 * u) + 260 * q);
-    f1k_wave_fence();
+    lq_wave_fence();
 #pragma unroll
     for (int u = 0; u < 2; u++) {
         v2f e0[4] = {c[u][0].xy, c[u][1].xy, c[u][2].xy, c[u][3].xy};
@@ -139,5 +132,5 @@ __device__ __forceinline__ void fft1024_wave_rt(float2 (&v)[16], float2 *B, floa
             *reinterpret_cast<v4f *>(B + 2 * p2 + 16 * (t2 + 8 * u) + 260 * sidx) = val;
         }
     }
-    f1k_wave_fence();
+    lq_wave_fence();
 }

@@ -262,6 +262,12 @@ ROWS = [
     # L > 32
     Row("generic", "crcf", 1.3, 20, 16, "generic/", n=12000),
 ]
+# every even L the launchers instantiate (2 .. 32) that no row above reaches:
+# k_resamp3 on rrrf, k_resamp4 on crcf, 3000 inputs (two tile seams and more)
+ROWS += [Row("r3-L%d" % L, "rrrf", 1.3, L // 2, 16, "resamp3/const", n=3000, cut=1500)
+         for L in range(2, 34, 2) if L != 14]
+ROWS += [Row("r4-L%d" % L, "crcf", 1.3, L // 2, 16, "resamp4/up", n=3000, cut=1500)
+         for L in range(4, 32, 2)]      # L = 14 too: the rows above run it at npfb = 64, its own instantiation
 ROW = {r.name: r for r in ROWS}
 # a call of at least 2^16 inputs builds the periodic plan; at r = 1.5 it
 # repeats every 256 outputs, so 2^16 + 5003 inputs wrap it hundreds of times
@@ -576,11 +582,12 @@ def ms_split(rate):
 
 
 class MsCase:
-    """msresamp at `rate`, As = 60: resamp (m = 7, fc = 0.4, 64 banks) then
-    the interpolating half-bands, or the decimating half-bands then resamp."""
+    """msresamp at `rate`, As = 60 unless given: resamp (m = 7, fc = 0.4, 64
+    banks) then the interpolating half-bands, or the decimating half-bands
+    then resamp."""
 
-    def __init__(self, t, rate, kind, n, cut, seam_out=None):
-        self.t, self.rate, self.kind, self.n, self.cut, self.As = t, float(np.float32(rate)), kind, n, cut, 60.0
+    def __init__(self, t, rate, kind, n, cut, seam_out=None, As=60.0):
+        self.t, self.rate, self.kind, self.n, self.cut, self.As = t, float(np.float32(rate)), kind, n, cut, As
         self.typ, self.ns, self.ra = ms_split(self.rate)
         self.M = 1 << self.ns
         self.stages = ms2_stages(self.ns, 0.4, self.As)
@@ -600,7 +607,8 @@ class MsCase:
             spans += [(cut - 60, cut), (n - 45, n)] + ([(0, 30)] if kind == "burst" else [])
             for lo, hi in spans:
                 env[max(lo, 0):min(max(hi, 0), n)] = 1.0
-        r = np.random.default_rng(zlib.crc32(("msresamp %s %g %s" % (t, rate, kind)).encode()))
+        seed = "msresamp %s %g %s" % (t, rate, kind) + ("" if As == 60.0 else " %g" % As)
+        r = np.random.default_rng(zlib.crc32(seed.encode()))
         if t == "rrrf":
             self.x = (r.uniform(-0.5, 0.5, n) * env).astype(np.float32)
         else:
@@ -657,10 +665,18 @@ MS_ROWS = [("crcf", 2.6, 12000, 5000, 6), ("rrrf", 2.6, 12000, 5000, 0), ("cccf"
            ("rrrf", 0.09, 40003, 15001, 0)]
 
 
-def ms_query(t, rate, n):
+# (As, fused stage m): the semi-lengths of the fused stage (3 .. 12) that
+# neither MS_ROWS (4, 5, 6) nor test_gpu_parity.py's interpolating chain (3, 4,
+# 6, 8) reaches, each by its stop-band attenuation at r = 2.6 (one stage,
+# fc = 0.2); crcf, 3000 inputs: 3900 resampler outputs, 16 tiles and more
+MS_HB_ROWS = [(68.0, 7), (85.0, 9), (94.0, 10), (102.0, 11), (110.0, 12)]
+MS_HB_RATE, MS_HB_N, MS_HB_CUT = 2.6, 3000, 1500
+
+
+def ms_query(t, rate, n, As=60.0):
     import liquidmi as LQ
     with _Environ({"LQ_RESAMP_INPUT_PLAN": "0"}):
-        return LQ.msresamp_route(t, float(np.float32(rate)), 60.0, n)
+        return LQ.msresamp_route(t, float(np.float32(rate)), As, n)
 
 
 @functools.lru_cache(maxsize=None)
@@ -670,6 +686,13 @@ def mscase(t, rate, kind):
     _, _, n, cut, _ = next(r for r in MS_ROWS if r[:2] == (t, rate))
     route, tile, hm = ms_query(t, rate, n)
     return MsCase(t, rate, kind, n, cut, tile if route.startswith("resamp4") else None)
+
+
+@functools.lru_cache(maxsize=None)
+def mshbcase(As, kind):
+    """The MS_HB_ROWS case at stop-band attenuation As."""
+    route, tile, hm = ms_query("crcf", MS_HB_RATE, MS_HB_N, As)
+    return MsCase("crcf", MS_HB_RATE, kind, MS_HB_N, MS_HB_CUT, tile, As)
 
 
 class Ms2Case:

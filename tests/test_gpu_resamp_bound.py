@@ -298,7 +298,7 @@ def _ms_run(c, way):
         # 1, 3, 5; one chain input either side of the one that emits the
         # resampler tile's first output; the end of the loud burst at cut
         scale = 1 if c.typ == 0 else c.M
-        tile = RB.ms_query(c.t, c.rate, c.n)[1]
+        tile = RB.ms_query(c.t, c.rate, c.n, c.As)[1]
         seam = int(c.idx[tile]) * scale if tile < len(c.idx) else c.n // 3
         e = sorted({0, 1, 4, 9, seam - 1, seam + 1, c.cut, c.n})
         return np.concatenate([g.execute(x[a:b]).copy() for a, b in zip(e[:-1], e[1:])])
@@ -332,6 +332,23 @@ def test_msresamp_bound(t, rate, n, cut, hm, way):
         r = c.check(y, way)
         print("r_gpu msresamp %s %g %s %s %.4f r_oracle %.4f ratio %.2f"
               % (t, rate, kind, way, r["worst"], c.r_oracle, r["worst"] / c.r_oracle))
+        assert r["worst"] <= MARGIN * c.r_oracle
+
+
+@pytest.mark.parametrize("way", ["one", "ragged", "wg3"])
+@pytest.mark.parametrize("As,hm", RB.MS_HB_ROWS)
+def test_msresamp_bound_fused_stage_lengths(As, hm, way):
+    """The fused stage's semi-lengths no other test reaches (RB.MS_HB_ROWS),
+    the route asserted as above, the same bound and margin."""
+    route, tile, got = RB.ms_query("crcf", RB.MS_HB_RATE, RB.MS_HB_N, As)
+    assert (route, got) == ("resamp4/up", hm) and tile == 256 - ((2 * hm - 1 + 3) & ~3)
+    for kind in RB.KINDS:
+        c = RB.mshbcase(As, kind)
+        y = _ms_run(c, way)
+        assert len(y) == len(c.y64)
+        r = c.check(y, way)
+        print("r_gpu msresamp As %g stage m %d %s %s %.4f r_oracle %.4f ratio %.2f"
+              % (As, hm, kind, way, r["worst"], c.r_oracle, r["worst"] / c.r_oracle))
         assert r["worst"] <= MARGIN * c.r_oracle
 
 

@@ -238,6 +238,19 @@ def test_msresamp_oracle_meets_the_cascaded_bound(t, rate, kind):
         assert np.count_nonzero(c.A == 0) > 0
 
 
+@pytest.mark.parametrize("kind", RB.KINDS)
+@pytest.mark.parametrize("As,hm", RB.MS_HB_ROWS)
+def test_msresamp_oracle_meets_the_cascaded_bound_at_every_fused_stage_length(As, hm, kind):
+    route, tile, got = RB.ms_query("crcf", RB.MS_HB_RATE, RB.MS_HB_N, As)
+    c = RB.mshbcase(As, kind)
+    assert (route, got) == ("resamp4/up", hm) and tile == 256 - ((2 * hm - 1 + 3) & ~3) and c.stages[-1][0] == hm
+    y = c.oracle([c.cut])
+    assert len(y) == len(c.y64)
+    r = c.check(y, "oracle")
+    print("r_oracle msresamp As %g (stage m %d) %s %.4f (T = %d)" % (As, hm, kind, r["worst"], c.T))
+    assert r["worst"] <= 1.0
+
+
 def test_msresamp_rows_reach_the_fused_and_the_unfused_chain():
     """The stage designs restate the library's (the fused stage's m is the
     query's), and the rows reach the fused launch -- its tile shorter by the
