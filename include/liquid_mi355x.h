@@ -915,6 +915,16 @@ int liquid_mi355x_firdecim_route(int _kind, unsigned int _M, unsigned int _h_len
                                  unsigned long long _nout);
 unsigned int liquid_mi355x_firdecim_tile(int _route);
 unsigned int liquid_mi355x_firdecim_grid_cap(int _kind, unsigned int _M, unsigned int _h_len, int _route);
+/* Which kernel a firinterp or firpfb device call takes for _M phases of _L
+ * taps each (firinterp: _L = ceil(h_len / M); firpfb: floor) and an output
+ * pointer that is (_y_aligned16) or is not 16-byte aligned, computed by the
+ * launch's own decision: 0 the plain kernel (complex taps, _L > 32, _M > 64,
+ * an unaligned output, or taps, tile and staged outputs past 64 KB of LDS),
+ * else the register-window kernel's tap class 8, 12, 16, 20, 24 or 32. */
+int liquid_mi355x_firinterp_route(int _kind, unsigned int _M, unsigned int _L, int _y_aligned16);
+/* The longest phase, in taps, a firinterp or firpfb object accepts (the plain
+ * kernel's LDS); _create with a longer one exits with a message. */
+unsigned int liquid_mi355x_firinterp_max_taps(int _kind);
 /* Which kernel the first block call of _nx inputs takes on a fresh resamp
  * object (_kind as above; no GPU call), computed by the launch's own
  * decision, and in *_tile (may be NULL) its tile: inputs per wave tile for

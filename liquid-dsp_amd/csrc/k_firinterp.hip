@@ -8,6 +8,9 @@
 #include "lq_fir.h"
 #include "lq_kernels.h"
 
+#include <cstdio>
+#include <cstdlib>
+
 namespace {
 
 // one input sample per lane -> M outputs; hpoly[p*L + l] = h'[p + l*M]
@@ -117,30 +120,52 @@ __global__ __launch_bounds__(NT) void k_firinterp_t(const typename kt<KIND>::T *
 
 } // namespace
 
+// the launch's decision: 0 for the plain kernel, else the LT class of
+// k_firinterp_t (real taps, L <= 32, M <= 64, a 16-byte aligned output, and
+// taps + tile + staged outputs within 64 KB of LDS, *lds2)
+static int firinterp_route(int kind, unsigned int M, unsigned int L, bool y_aligned16, size_t *lds2)
+{
+    if (kind == 2 || L > 32 || M > 64 || !y_aligned16) return 0;
+    const int LT = L <= 8 ? 8 : L <= 12 ? 12 : L <= 16 ? 16 : L <= 20 ? 20 : L <= 24 ? 24 : 32;
+    const size_t es = elem_size(kind);
+    *lds2 = (((size_t)M * LT * 4 + 15) & ~(size_t)15) + (((size_t)NT + LT - 1 + 3) & ~(size_t)3) * es +
+            (size_t)NT * M * es;
+    return *lds2 <= 64 * 1024 ? LT : 0;
+}
+
+extern "C" int lqk_firinterp_route(int kind, unsigned int M, unsigned int L, int y_aligned16)
+{
+    size_t lds2 = 0;
+    return firinterp_route(kind, M, L, y_aligned16 != 0, &lds2);
+}
+
+// the plain kernel's tile and history, (NT + L) samples, within the dynamic
+// LDS budget (it has no static segment): the longest phase any shape can run
+extern "C" unsigned int lqk_firinterp_max_taps(int kind) { return (unsigned int)(FIR_LDS_MAX / elem_size(kind)) - NT; }
+
 extern "C" void lqk_firinterp(int kind, const void *hpoly, unsigned int M, unsigned int L, float sre, float sim,
                               const void *hist, const void *x, unsigned long long n, void *y, void *stream)
 {
     if (n == 0) return;
     hipStream_t st = (hipStream_t)stream;
     const unsigned nb = (unsigned)((n + NT - 1) / NT);
-    // real taps, L <= 32, 16-byte aligned output: the register-window kernel
-    if (kind != 2 && L <= 32 && M <= 64 && ((uintptr_t)y & 15) == 0) {
-        const int LT = L <= 8 ? 8 : L <= 12 ? 12 : L <= 16 ? 16 : L <= 20 ? 20 : L <= 24 ? 24 : 32;
-        const size_t es = elem_size(kind);
-        const size_t lds2 = (((size_t)M * LT * 4 + 15) & ~(size_t)15) + (((size_t)NT + LT - 1 + 3) & ~(size_t)3) * es +
-                            (size_t)NT * M * es;
-        if (lds2 <= 64 * 1024) {
-            lq_switch<0, 1>(kind, [&](auto k) {
-                typedef typename kt<k>::T T;
-                lq_switch<8, 12, 16, 20, 24, 32>(LT, [&](auto lt) {
-                    hipLaunchKernelGGL((k_firinterp_t<k, lt>), dim3(nb), dim3(NT), lds2, st, (const T *)hist,
-                                       (const T *)x, (long long)n, (int)M, (int)L, (const float *)hpoly, sre, sim,
-                                       (T *)y);
-                });
+    size_t lds2 = 0;
+    const int LT = firinterp_route(kind, M, L, ((uintptr_t)y & 15) == 0, &lds2);
+    if (LT) {   // the register-window kernel
+        lq_switch<0, 1>(kind, [&](auto k) {
+            typedef typename kt<k>::T T;
+            lq_switch<8, 12, 16, 20, 24, 32>(LT, [&](auto lt) {
+                hipLaunchKernelGGL((k_firinterp_t<k, lt>), dim3(nb), dim3(NT), lds2, st, (const T *)hist,
+                                   (const T *)x, (long long)n, (int)M, (int)L, (const float *)hpoly, sre, sim,
+                                   (T *)y);
             });
-            LQ_CHECK_LAUNCH();
-            return;
-        }
+        });
+        LQ_CHECK_LAUNCH();
+        return;
+    }
+    if (L > lqk_firinterp_max_taps(kind)) {   // refused at create (host/firdecim.c, host/firpfb.c)
+        fprintf(stderr, "error: firinterp: %u taps per phase exceed the GPU kernel limit\n", L);
+        exit(1);
     }
     const size_t lds = (size_t)(NT + L) * elem_size(kind);
     fir_kind(kind, [&](auto k) {

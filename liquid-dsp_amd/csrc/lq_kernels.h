@@ -140,6 +140,11 @@ unsigned int lqk_firdecim_route_cap(int kind, unsigned int M, unsigned int hlen,
 void lqk_firinterp(int kind, const void *hpoly /* M x L, h[p + l*M] */, unsigned int M,
                    unsigned int L, float scale_re, float scale_im, const void *hist, const void *x,
                    unsigned long long n, void *y, void *stream);
+/* the kernel lqk_firinterp takes for L taps per phase (its own decision):
+ * 0 the plain kernel, else the LT class of the register-window kernel */
+int lqk_firinterp_route(int kind, unsigned int M, unsigned int L, int y_aligned16);
+/* the longest phase (taps) lqk_firinterp can run: the plain kernel's LDS */
+unsigned int lqk_firinterp_max_taps(int kind);
 
 /* ---------------------------------------------------------------- firpfbch2 analyzer
  * nblocks consecutive analyzer blocks over x (nblocks*M/2 samples); hist holds

@@ -249,6 +249,9 @@ static lq_interp *lq_interp_create(int kind, unsigned int M, const float *h, uns
     if (M < 2) LQ_FAIL("error: firinterp_%s_create(), interp factor must be greater than 1\n", lq_ext(kind));
     if (hlen < M)
         LQ_FAIL("error: firinterp_%s_create(), filter length cannot be less than interp factor\n", lq_ext(kind));
+    if ((hlen + M - 1) / M > lqk_firinterp_max_taps(kind))
+        LQ_FAIL("error: firinterp_%s_create(), filter length (%u taps per phase) exceeds the GPU kernel limit (%u)\n",
+                lq_ext(kind), (hlen + M - 1) / M, lqk_firinterp_max_taps(kind));
     lqrt_require_device("firinterp_create");
     lq_interp *q = (lq_interp *)lq_xmalloc(sizeof(*q));
     q->kind = kind;
@@ -383,6 +386,14 @@ static void lq_interp_block(lq_interp *q, const void *x, unsigned long long n, v
         lq_interp_block_dev(_q->e, _dx, _n, _dy);                                                   \
     }                                                                                               \
     void NAME##_set_stream(NAME _q, void *_s) { lq_ctx_set_stream(&_q->e->ctx, _s); }
+
+/* the route and limit queries of include/liquid_mi355x.h: the kernels' own decision */
+int liquid_mi355x_firinterp_route(int _kind, unsigned int _M, unsigned int _L, int _y_aligned16)
+{
+    return lqk_firinterp_route(_kind, _M, _L, _y_aligned16);
+}
+
+unsigned int liquid_mi355x_firinterp_max_taps(int _kind) { return lqk_firinterp_max_taps(_kind); }
 
 LQ_FIRINTERP_FRONT(firinterp_rrrf, LQ_RRRF, float, float, float)
 LQ_FIRINTERP_FRONT(firinterp_crcf, LQ_CRCF, liquid_float_complex, float, liquid_float_complex)

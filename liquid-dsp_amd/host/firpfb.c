@@ -40,6 +40,9 @@ static lq_pfb *lq_pfb_create(int kind, unsigned int M, const float *h, unsigned 
     if (hlen == 0) LQ_FAIL("error: firpfb_%s_create(), filter length must be greater than zero\n", lq_ext(kind));
     if (hlen < M)
         LQ_FAIL("error: firpfb_%s_create(), filter length must be at least the number of filters\n", lq_ext(kind));
+    if (hlen / M > lqk_firinterp_max_taps(kind))
+        LQ_FAIL("error: firpfb_%s_create(), filter length (%u taps per filter) exceeds the GPU kernel limit (%u)\n",
+                lq_ext(kind), hlen / M, lqk_firinterp_max_taps(kind));
     lqrt_require_device("firpfb_create");
     lq_pfb *q = (lq_pfb *)lq_xmalloc(sizeof(*q));
     q->kind = kind;

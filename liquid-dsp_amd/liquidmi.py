@@ -89,6 +89,26 @@ def firdecim_grid_cap(t, M, hlen, route):
     return int(lib().liquid_mi355x_firdecim_grid_cap(_KINDS[t], M, hlen, FIRDECIM_ROUTES.index(route)))
 
 
+def firinterp_route(t, M, L, aligned16=True):
+    """The kernel a firinterp / firpfb device call takes for M phases of L
+    taps (no GPU call): 0 the plain kernel, else the register-window kernel's
+    tap class (8, 12, 16, 20, 24, 32)."""
+    return int(lib().liquid_mi355x_firinterp_route(_KINDS[t], M, L, 1 if aligned16 else 0))
+
+
+def firinterp_max_taps(t):
+    """The longest phase, in taps, a firinterp or firpfb object accepts."""
+    return int(lib().liquid_mi355x_firinterp_max_taps(_KINDS[t]))
+
+
+def fftfilt_nfft(t, hlen):
+    """Points of fftfilt's segment transform for hlen taps (lqk_fftfilt_nfft):
+    4096, 8192, or 0 where the object runs the direct FIR engine instead."""
+    fn = lib().lqk_fftfilt_nfft
+    fn.restype, fn.argtypes = C.c_uint, [C.c_int, C.c_uint]
+    return int(fn(1 if t == RRRF else 0, hlen))
+
+
 # liquid_mi355x_resamp_route's and liquid_mi355x_resamp2_route's codes, by name
 RESAMP_ROUTES = ("resamp3/const", "resamp3/stride", "resamp/", "generic/", "resamp4/up", "resamp4/up_r4",
                  "resamp4/down", "resamp4/down_dn")
@@ -491,6 +511,8 @@ def _declare(L):
         "liquid_mi355x_firdecim_route": (i, [i, u, u, i, ull]),
         "liquid_mi355x_firdecim_tile": (u, [i]),
         "liquid_mi355x_firdecim_grid_cap": (u, [i, u, u, i]),
+        "liquid_mi355x_firinterp_route": (i, [i, u, u, i]),
+        "liquid_mi355x_firinterp_max_taps": (u, [i]),
         "liquid_mi355x_resamp_route": (i, [i, f, u, u, ull, vp]),
         "liquid_mi355x_resamp2_route": (i, [i, u, ull, vp]),
         "liquid_mi355x_msresamp_route": (i, [i, f, f, ull, vp, vp]),
@@ -821,6 +843,12 @@ class FirInterp(_Obj):
     def reset(self):
         self._fn("_reset")(self.q)
 
+    def execute_block_dev(self, dx, n, dy):
+        self._fn("_execute_block_dev")(self.q, dx, n, dy)
+
+    def synchronize(self):
+        lib().liquid_mi355x_device_synchronize()
+
 
 class FftFilt(_Obj):
     family = "fftfilt_%s"
@@ -963,6 +991,13 @@ class FirPfb(_Obj):
         y = np.zeros(len(x) * self.M, _out_dtype(self.t))
         self._fn("_execute_block")(self.q, ptr(x), len(x), ptr(y))
         return y.reshape(len(x), self.M)
+
+    def execute_block_dev(self, dx, n, dy):
+        """n inputs at dx -> n * M outputs at dy, y[t * M + i] (device pointers)"""
+        self._fn("_execute_block_dev")(self.q, dx, n, dy)
+
+    def synchronize(self):
+        lib().liquid_mi355x_device_synchronize()
 
 
 class Resamp(_Obj):
