@@ -925,6 +925,39 @@ int liquid_mi355x_firinterp_route(int _kind, unsigned int _M, unsigned int _L, i
 /* The longest phase, in taps, a firinterp or firpfb object accepts (the plain
  * kernel's LDS); _create with a longer one exits with a message. */
 unsigned int liquid_mi355x_firinterp_max_taps(int _kind);
+/* Which kernels a transform of the FFT plan API takes for _n points read from
+ * a pointer that is (_aligned16) or is not 16-byte aligned, computed by the
+ * launch's own decision (no GPU call).  Bits 0-3 the family below; bit 4 the
+ * 16-byte loads of the 8192- and 16384-point kernels; bits 8-12 and 16-20 lg
+ * N1 and lg N2 of the two-pass split (columns in k_fft2p_cols_r / k_bs_cols_r
+ * <N1 / 256>; rows in k_bs_rows_s<N2 / 16> when bit 5 is set, else in
+ * k_fft2p_rows_r / k_bs_rows_r<N2 / 256>); bits 24-28 lg M of Bluestein's
+ * padded transform (BLUESTEIN: its M-point transforms take the route of M). */
+enum {
+    LIQUID_MI355X_FFT_REFUSED = 0,          /* 0, or past 2^24 (2^23 when not a power of two) */
+    LIQUID_MI355X_FFT_DFT = 1,              /* direct sums: n = 1 and other n <= 16 */
+    LIQUID_MI355X_FFT_BATCH = 2,            /* k_fft_batch<n>: 2, 4, 8, 16 */
+    LIQUID_MI355X_FFT_SMALL = 3,            /* k_fftsmall_batch<n / 16>: 32, 64, 128 */
+    LIQUID_MI355X_FFT_R16 = 4,              /* k_fftr16_batch<n / 256>: 256, 512, 2048 */
+    LIQUID_MI355X_FFT_1024 = 5,
+    LIQUID_MI355X_FFT_4096 = 6,
+    LIQUID_MI355X_FFT_8192 = 7,
+    LIQUID_MI355X_FFT_16384 = 8,
+    LIQUID_MI355X_FFT_FOUR_STEP = 9,        /* powers of two from 32768, two passes */
+    LIQUID_MI355X_FFT_BLUESTEIN = 10,       /* M <= 4096: chirp products as kernels of their own */
+    LIQUID_MI355X_FFT_BLUESTEIN_FUSED = 11  /* M > 4096: chirp products inside the two passes */
+};
+int liquid_mi355x_fft_route(unsigned int _n, int _aligned16);
+/* spgram's reduction as the launches decide it (no GPU call).  _route: the
+ * path of a call of _n samples -- 0 gather, batch transform and k_spg_part,
+ * else k_spg_fused1024<S, HALF, TR> as 1 + 2 HALF + 4 TR; _chunk: transforms
+ * per chunk; _fold_group: chunks per first-level fold group (more chunks fold
+ * in two levels); _batch_samples: transforms per launch batch of the plain
+ * path, in samples (batch_samples / nfft transforms). */
+int liquid_mi355x_spgram_route(int _real_in, unsigned int _nfft, unsigned int _window_len, unsigned long long _n);
+unsigned int liquid_mi355x_spgram_chunk(void);
+unsigned int liquid_mi355x_spgram_fold_group(void);
+unsigned long long liquid_mi355x_spgram_batch_samples(void);
 /* Which kernel the first block call of _nx inputs takes on a fresh resamp
  * object (_kind as above; no GPU call), computed by the launch's own
  * decision, and in *_tile (may be NULL) its tile: inputs per wave tile for

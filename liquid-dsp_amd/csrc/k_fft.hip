@@ -218,10 +218,11 @@ void bs_rows(int N2, const float2 *work, float2 *dst, long long n, long long M, 
 void fft_four_step(unsigned n, int dir, const void *x, void *y, long long batch, void *work, const float2 *fine,
                    hipStream_t st)
 {
-    const int lg = lg2(n), sh = lg - 12;
-    // the larger factor on the column pass (N2 <= N1 <= 4096 for n <= 2^24): for odd lg the
-    // 2^k-point column transforms with the twiddle run in registers
-    const int N1 = 1 << ((lg + 1) / 2), N2 = (int)(n / (unsigned)N1);
+    const int sh = lg2(n) - 12;
+    // the larger factor on the column pass (lqk_fft_route: N2 <= N1 <= 4096 for n <= 2^24): for
+    // odd lg the 2^k-point column transforms with the twiddle run in registers
+    const lqk_fft_route_t r = lqk_fft_route(n, 1);
+    const int N1 = (int)r.N1, N2 = (int)r.N2;
     // n >= 32768 here (8192 and 16384 run in one pass): N1 >= 256; N2 = 128
     // (n = 32768) runs its row pass in registers (fft_small16xR, the
     // Bluestein split's kernel; with the LDS Stockham passes the four-step
@@ -234,12 +235,12 @@ void fft_four_step(unsigned n, int dir, const void *x, void *y, long long batch,
     case 2048: launch_cols_r<8>(x, work, n, N2, dir, batch, fine, sh, st); break;
     default: launch_cols_r<16>(x, work, n, N2, dir, batch, fine, sh, st); break;
     }
-    switch (N2) {
-    case 64:
-    case 128:
+    if (r.rows_s) {
         if (dir > 0) bs_rows<+1, 0>(N2, ws, ys, n, n, N1, nullptr, 1.0f, batch, st);
         else bs_rows<-1, 0>(N2, ws, ys, n, n, N1, nullptr, 1.0f, batch, st);
-        break;
+        return;
+    }
+    switch (N2) {
     case 256: launch_rows_r<1>(work, y, n, N1, dir, batch, st); break;
     case 512: launch_rows_r<2>(work, y, n, N1, dir, batch, st); break;
     case 1024: launch_rows_r<4>(work, y, n, N1, dir, batch, st); break;
@@ -252,7 +253,8 @@ void fft_four_step(unsigned n, int dir, const void *x, void *y, long long batch,
 void fft_pow2(unsigned n, int dir, const void *x, void *y, long long batch, void *work, const float2 *fine,
               hipStream_t st)
 {
-    if (n <= 16384) lqk_fft_batch(n, dir, x, y, (unsigned long long)batch, st);   // 8192, 16384: one pass
+    if (lqk_fft_route(n, 1).family != LQK_FFT_FOUR_STEP)
+        lqk_fft_batch(n, dir, x, y, (unsigned long long)batch, st);   // up to 16384: one pass
     else fft_four_step(n, dir, x, y, batch, work, fine, st);
 }
 
@@ -284,30 +286,31 @@ __global__ void k_bs_kernel(long long n, long long M, const float2 *__restrict__
 }
 
 __global__ void k_bs_pre(const float2 *__restrict__ x, float2 *__restrict__ a, long long n, long long M,
-                         const float2 *__restrict__ c)
+                         long long batch, const float2 *__restrict__ c)
 {
     const long long e = (long long)blockIdx.x * NT + threadIdx.x;
-    const long long z = blockIdx.y;
     if (e >= M) return;
-    a[z * M + e] = e < n ? cmul(x[z * n + e], c[e]) : make_float2(0.f, 0.f);
+    const float2 ce = e < n ? c[e] : make_float2(0.f, 0.f);
+    for (long long z = blockIdx.y; z < batch; z += gridDim.y)
+        a[z * M + e] = e < n ? cmul(x[z * n + e], ce) : make_float2(0.f, 0.f);
 }
 
-__global__ void k_bs_mul(float2 *__restrict__ a, const float2 *__restrict__ B, long long M)
+__global__ void k_bs_mul(float2 *__restrict__ a, const float2 *__restrict__ B, long long M, long long batch)
 {
     const long long e = (long long)blockIdx.x * NT + threadIdx.x;
     if (e >= M) return;
-    const long long z = blockIdx.y;
-    a[z * M + e] = cmul(a[z * M + e], B[e]);
+    const float2 b = B[e];
+    for (long long z = blockIdx.y; z < batch; z += gridDim.y) a[z * M + e] = cmul(a[z * M + e], b);
 }
 
 __global__ void k_bs_post(const float2 *__restrict__ a, float2 *__restrict__ y, long long n, long long M,
-                          const float2 *__restrict__ c)
+                          long long batch, const float2 *__restrict__ c)
 {
     const long long k = (long long)blockIdx.x * NT + threadIdx.x;
-    const long long z = blockIdx.y;
     if (k >= n) return;
     const float inv = 1.0f / (float)M;
-    y[z * n + k] = cscale(cmul(a[z * M + k], c[k]), inv);
+    const float2 ck = c[k];
+    for (long long z = blockIdx.y; z < batch; z += gridDim.y) y[z * n + k] = cscale(cmul(a[z * M + k], ck), inv);
 }
 
 // ---------------------------------------------------------------- Bluestein, M > 4096
@@ -506,12 +509,8 @@ void bs_rows(int N2, const float2 *work, float2 *dst, long long n, long long M, 
 }
 
 // real-to-real transforms: fft_r2r_1d.c:95-250 (un-normalised, factor 2)
-__global__ void k_r2r(int type, int n, const float *__restrict__ x, float *__restrict__ y)
+__device__ __forceinline__ void r2r_row(int type, int n, int i, const float *__restrict__ xs, float *__restrict__ y)
 {
-    const int i = blockIdx.x * NT + threadIdx.x;
-    const long long z = blockIdx.y;
-    if (i >= n) return;
-    const float *xs = x + z * n;
     // phases pi*num/den with the integer numerator reduced modulo one period
     double acc = 0.0;
     switch (type) {
@@ -551,7 +550,14 @@ __global__ void k_r2r(int type, int n, const float *__restrict__ x, float *__res
         for (int k = 0; k < n; k++)
             acc += (double)xs[k] * sinpi((double)(((2LL * k + 1) * (2LL * i + 1)) % (8LL * n)) / (4.0 * n));
     }
-    y[z * n + i] = (float)(2.0 * acc);
+    y[i] = (float)(2.0 * acc);
+}
+
+__global__ void k_r2r(int type, int n, long long batch, const float *__restrict__ x, float *__restrict__ y)
+{
+    const int i = blockIdx.x * NT + threadIdx.x;
+    if (i >= n) return;
+    for (long long z = blockIdx.y; z < batch; z += gridDim.y) r2r_row(type, n, i, x + z * n, y + z * n);
 }
 
 } // namespace
@@ -578,17 +584,17 @@ extern "C" void lqk_fft_any(unsigned int n, int dir, const void *x, void *y, uns
         fprintf(stderr, "error: liquid-mi355x: transform size %u exceeds the GPU FFT limit (2^24, 2^23 non power of two)\n", n);
         exit(1);
     }
+    const lqk_fft_route_t r = lqk_fft_route(n, ((uintptr_t)x & 15) == 0);
     if (pow2) {
-        const float2 *fine = n > 16384 ? fine_table(n, (float2 *)work + (size_t)n * batch, st) : nullptr;
+        const float2 *fine = r.family == LQK_FFT_FOUR_STEP ? fine_table(n, (float2 *)work + (size_t)n * batch, st) : nullptr;
         fft_pow2(n, dir, x, y, (long long)batch, work, fine, st);
         return;
     }
-    if (n <= 16) {
+    if (r.family == LQK_FFT_DFT) {
         lqk_fft_batch(n, dir, x, y, batch, st);
         return;
     }
-    long long M = 1;
-    while (M < 2LL * n - 1) M <<= 1;
+    const long long M = (long long)r.M;
     float2 *a = (float2 *)work;
     float2 *B = a + M * (long long)batch;
     float2 *w4 = B + M;
@@ -601,11 +607,10 @@ extern "C" void lqk_fft_any(unsigned int n, int dir, const void *x, void *y, uns
     LQ_CHECK_LAUNCH();
     const float2 *tfine = M > 4096 ? fine_table((unsigned long long)M, ct + n, st) : nullptr;
     fft_pow2((unsigned)M, +1, B, B, 1, w4, tfine, st);
-    if (M > 4096) {
+    if (r.family == LQK_FFT_BLUESTEIN_FUSED) {
         // the fused four-pass form (above); N1 >= N2 as fft_four_step splits
-        const int lg = lg2((unsigned long long)M);
-        const int N1 = 1 << ((lg + 1) / 2), N2 = (int)(M / N1);
-        const int sh = lg - 12;
+        const int N1 = (int)r.N1, N2 = (int)r.N2;
+        const int sh = lg2((unsigned long long)M) - 12;
         const long long bt = (long long)batch;
         bs_cols<+1, true>(N1, (const float2 *)x, w4, (long long)n, M, N2, ct, tfine, sh, bt, st);
         bs_rows<+1, 1>(N2, w4, a, (long long)n, M, N1, B, 1.f, bt, st);
@@ -613,23 +618,27 @@ extern "C" void lqk_fft_any(unsigned int n, int dir, const void *x, void *y, uns
         bs_rows<-1, 2>(N2, w4, (float2 *)y, (long long)n, M, N1, ct, 1.0f / (float)M, bt, st);
         return;
     }
-    const dim3 gM((unsigned)((M + NT - 1) / NT), (unsigned)batch);
-    hipLaunchKernelGGL(k_bs_pre, gM, dim3(NT), 0, st, (const float2 *)x, a, (long long)n, M, (const float2 *)ct);
+    // the batch on grid.y up to LQ_GRID_Y_MAX rows; the kernels stride over the rest
+    const unsigned gy = (unsigned)(batch < LQ_GRID_Y_MAX ? batch : LQ_GRID_Y_MAX);
+    const dim3 gM((unsigned)((M + NT - 1) / NT), gy);
+    hipLaunchKernelGGL(k_bs_pre, gM, dim3(NT), 0, st, (const float2 *)x, a, (long long)n, M, (long long)batch,
+                       (const float2 *)ct);
     LQ_CHECK_LAUNCH();
     fft_pow2((unsigned)M, +1, a, a, (long long)batch, w4, nullptr, st);
-    hipLaunchKernelGGL(k_bs_mul, gM, dim3(NT), 0, st, a, (const float2 *)B, M);
+    hipLaunchKernelGGL(k_bs_mul, gM, dim3(NT), 0, st, a, (const float2 *)B, M, (long long)batch);
     LQ_CHECK_LAUNCH();
     fft_pow2((unsigned)M, -1, a, a, (long long)batch, w4, nullptr, st);
-    const dim3 gn((unsigned)((n + NT - 1) / NT), (unsigned)batch);
+    const dim3 gn((unsigned)((n + NT - 1) / NT), gy);
     hipLaunchKernelGGL(k_bs_post, gn, dim3(NT), 0, st, (const float2 *)a, (float2 *)y, (long long)n, M,
-                       (const float2 *)ct);
+                       (long long)batch, (const float2 *)ct);
     LQ_CHECK_LAUNCH();
 }
 
 extern "C" void lqk_fft_r2r(int type, unsigned int n, const void *x, void *y, unsigned long long batch, void *stream)
 {
     if (batch == 0 || n == 0) return;
-    const dim3 g((n + NT - 1) / NT, (unsigned)batch);
-    hipLaunchKernelGGL(k_r2r, g, dim3(NT), 0, (hipStream_t)stream, type, (int)n, (const float *)x, (float *)y);
+    const dim3 g((n + NT - 1) / NT, (unsigned)(batch < LQ_GRID_Y_MAX ? batch : LQ_GRID_Y_MAX));
+    hipLaunchKernelGGL(k_r2r, g, dim3(NT), 0, (hipStream_t)stream, type, (int)n, (long long)batch, (const float *)x,
+                       (float *)y);
     LQ_CHECK_LAUNCH();
 }

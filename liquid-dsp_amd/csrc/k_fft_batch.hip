@@ -468,10 +468,9 @@ void launch_fft4096(const void *x, void *y, long long batch, int dir, float s1, 
 
 // 8192 and 16384: 16-byte loads where x allows them
 void launch_fft8192(const void *x, void *y, long long batch, int dir, float s1, float s2, int u1, int u2,
-                    hipStream_t st)
+                    bool a16, hipStream_t st)
 {
     const unsigned grid = lqrt_grid((unsigned long long)batch, 2048);
-    const bool a16 = ((uintptr_t)x & 15) == 0;
     lq_switch<+1, -1>(dir > 0 ? +1 : -1, [&](auto d) {
         lq_switch<1, 0>(a16, [&](auto a) {
             hipLaunchKernelGGL((k_fft8192_batch<d, a != 0>), dim3(grid), dim3(256), 0, st, (const float2 *)x,
@@ -482,10 +481,9 @@ void launch_fft8192(const void *x, void *y, long long batch, int dir, float s1, 
 }
 
 void launch_fft16384(const void *x, void *y, long long batch, int dir, float s1, float s2, int u1, int u2,
-                     hipStream_t st)
+                     bool a16, hipStream_t st)
 {
     const unsigned grid = lqrt_grid((unsigned long long)batch, 1024);
-    const bool a16 = ((uintptr_t)x & 15) == 0;
     lq_switch<+1, -1>(dir > 0 ? +1 : -1, [&](auto d) {
         lq_switch<1, 0>(a16, [&](auto a) {
             hipLaunchKernelGGL((k_fft16384_batch<d, a != 0>), dim3(grid), dim3(512), 0, st, (const float2 *)x,
@@ -495,36 +493,89 @@ void launch_fft16384(const void *x, void *y, long long batch, int dir, float s1,
     LQ_CHECK_LAUNCH();
 }
 
+// the one-pass kernels' dispatch: the family lq_fft_batch_scaled launches for
+// n points read from a pointer that is or is not 16-byte aligned
+int fft_batch_family(unsigned n)
+{
+    if (n == 0) return LQK_FFT_REFUSED;
+    if (n & (n - 1)) return n <= 8192 ? LQK_FFT_DFT : LQK_FFT_REFUSED;   // one workgroup per transform, n points of LDS
+    if (n == 1) return LQK_FFT_DFT;
+    if (n <= 16) return LQK_FFT_BATCH;
+    if (n <= 128) return LQK_FFT_SMALL;
+    switch (n) {
+    case 256:
+    case 512:
+    case 2048: return LQK_FFT_R16;
+    case 1024: return LQK_FFT_1024;
+    case 4096: return LQK_FFT_4096;
+    case 8192: return LQK_FFT_8192;
+    case 16384: return LQK_FFT_16384;
+    default: return LQK_FFT_REFUSED;
+    }
+}
+
 } // namespace
+
+extern "C" lqk_fft_route_t lqk_fft_route(unsigned int n, int aligned16)
+{
+    lqk_fft_route_t r = {LQK_FFT_REFUSED, 0, 0, 0, 0, 0};
+    const bool pow2 = n != 0 && (n & (n - 1)) == 0;
+    if (n == 0 || (pow2 && n > (1u << 24)) || (!pow2 && n > (1u << 23))) return r;
+    if ((pow2 && n <= 16384) || (!pow2 && n <= 16)) {   // one pass
+        r.family = fft_batch_family(n);
+        r.a16 = (r.family == LQK_FFT_8192 || r.family == LQK_FFT_16384) && aligned16;
+        return r;
+    }
+    // two passes over N1 x N2 points: the transform itself, or Bluestein's M >= 2n - 1
+    unsigned long long M = n;
+    if (!pow2) {
+        M = 1;
+        while (M < 2ull * n - 1) M <<= 1;
+        r.M = M;
+        if (M <= 4096) {   // chirp multiply, lq_fft_batch_scaled's M-point kernels, multiply, back
+            r.family = LQK_FFT_BLUESTEIN;
+            return r;
+        }
+    }
+    int lg = 0;
+    while ((1ull << lg) < M) lg++;
+    // the larger factor on the column pass (N2 <= N1 <= 4096 for M <= 2^24)
+    r.N1 = 1u << ((lg + 1) / 2);
+    r.N2 = (unsigned)(M / r.N1);
+    r.family = pow2 ? LQK_FFT_FOUR_STEP : LQK_FFT_BLUESTEIN_FUSED;
+    r.rows_s = r.N2 < 256;   // the row pass in k_bs_rows_s (registers, 16 x R points)
+    return r;
+}
 
 void lq_fft_batch_scaled(unsigned n, int dir, const void *x, void *y, long long batch, float s1, float s2, int u1,
                          int u2, hipStream_t st)
 {
     if (batch <= 0) return;
-    if (lq_switch<2, 4, 8, 16>(n, [&](auto N) { launch_fft_batch<N>(x, y, batch, dir, s1, s2, u1, u2, st); }) ||
-        lq_switch<32, 64, 128>(n, [&](auto N) { launch_fftsmall<N / 16>(x, y, batch, dir, s1, s2, u1, u2, st); }) ||
-        lq_switch<256, 512, 2048>(n, [&](auto N) { launch_fftr16<N / 256>(x, y, batch, dir, s1, s2, u1, u2, st); }))
+    const bool a16 = ((uintptr_t)x & 15) == 0;
+    switch (fft_batch_family(n)) {
+    case LQK_FFT_BATCH:
+        lq_switch<2, 4, 8, 16>(n, [&](auto N) { launch_fft_batch<N>(x, y, batch, dir, s1, s2, u1, u2, st); });
         return;
-    switch (n) {
-    case 1024: launch_fft1024(x, y, batch, dir, s1, s2, u1, u2, st); return;
-    case 4096: launch_fft4096(x, y, batch, dir, s1, s2, u1, u2, st); return;
-    case 8192: launch_fft8192(x, y, batch, dir, s1, s2, u1, u2, st); return;
-    case 16384: launch_fft16384(x, y, batch, dir, s1, s2, u1, u2, st); return;
-    default: break;
-    }
-    if (n == 1) {
-        hipLaunchKernelGGL(k_dft_batch, dim3((unsigned)batch), dim3(64), 16, st, 1, (const float2 *)x, (float2 *)y,
-                           batch, dir, s1, s2, u1, u2);
+    case LQK_FFT_SMALL:
+        lq_switch<32, 64, 128>(n, [&](auto N) { launch_fftsmall<N / 16>(x, y, batch, dir, s1, s2, u1, u2, st); });
+        return;
+    case LQK_FFT_R16:
+        lq_switch<256, 512, 2048>(n, [&](auto N) { launch_fftr16<N / 256>(x, y, batch, dir, s1, s2, u1, u2, st); });
+        return;
+    case LQK_FFT_1024: launch_fft1024(x, y, batch, dir, s1, s2, u1, u2, st); return;
+    case LQK_FFT_4096: launch_fft4096(x, y, batch, dir, s1, s2, u1, u2, st); return;
+    case LQK_FFT_8192: launch_fft8192(x, y, batch, dir, s1, s2, u1, u2, a16, st); return;
+    case LQK_FFT_16384: launch_fft16384(x, y, batch, dir, s1, s2, u1, u2, a16, st); return;
+    case LQK_FFT_DFT:
+        hipLaunchKernelGGL(k_dft_batch, dim3((unsigned)batch), dim3(n == 1 ? 64 : 256),
+                           n == 1 ? 16 : (size_t)n * sizeof(float2), st, (int)n, (const float2 *)x, (float2 *)y, batch,
+                           dir, s1, s2, u1, u2);
         LQ_CHECK_LAUNCH();
         return;
-    }
-    if (n > 8192) {
+    default:
         fprintf(stderr, "error: liquid-mi355x: non power-of-two transform size %u not supported\n", n);
         exit(1);
     }
-    hipLaunchKernelGGL(k_dft_batch, dim3((unsigned)batch), dim3(256), (size_t)n * sizeof(float2), st, (int)n, (const float2 *)x,
-                       (float2 *)y, batch, dir, s1, s2, u1, u2);
-    LQ_CHECK_LAUNCH();
 }
 
 extern "C" void lqk_fft_batch(unsigned int n, int dir, const void *x, void *y, unsigned long long batch,

@@ -10,6 +10,9 @@
 // |X|^2.
 #include <hip/hip_runtime.h>
 
+#include <cstdio>
+#include <cstdlib>
+
 #include "lq_device.h"
 #include "lq_fft1024.h"
 #include "lq_kernels.h"
@@ -24,19 +27,21 @@ __device__ __forceinline__ float2 as_c(float2 v) { return v; }
 // out[t][i] = ext[e_t + 1 + i] * w[i] (i < W), 0 (W <= i < nfft); ext = hist(W) ++ x
 template <typename S>
 __global__ __launch_bounds__(NT) void k_spg_gather(const S *__restrict__ hist, int W, const S *__restrict__ x,
-                                                   const long long *__restrict__ ends, const float *__restrict__ w,
-                                                   int nfft, float2 *__restrict__ out)
+                                                   const long long *__restrict__ ends, long long T,
+                                                   const float *__restrict__ w, int nfft, float2 *__restrict__ out)
 {
     const int i = blockIdx.x * NT + threadIdx.x;
-    const long long t = blockIdx.y;
     if (i >= nfft) return;
-    float2 v = make_float2(0.f, 0.f);
-    if (i < W) {
-        const long long j = ends[t] + 1 + i;
-        const float2 s = as_c(j < W ? hist[j] : x[j - W]);
-        v = make_float2(s.x * w[i], s.y * w[i]);
+    const float wi = i < W ? w[i] : 0.0f;
+    for (long long t = blockIdx.y; t < T; t += gridDim.y) {   // T past LQ_GRID_Y_MAX: strided
+        float2 v = make_float2(0.f, 0.f);
+        if (i < W) {
+            const long long j = ends[t] + 1 + i;
+            const float2 s = as_c(j < W ? hist[j] : x[j - W]);
+            v = make_float2(s.x * wi, s.y * wi);
+        }
+        out[t * nfft + i] = v;
     }
-    out[t * nfft + i] = v;
 }
 
 __device__ __forceinline__ float pwr(float2 v)
@@ -60,14 +65,17 @@ __global__ __launch_bounds__(NT) void k_spg_part(const float2 *__restrict__ X, l
 #pragma clang fp contract(off)
     const int k = blockIdx.x * NT + threadIdx.x;
     if (k >= nfft) return;
-    const long long t0 = (long long)blockIdx.y * SPG_TC;
-    const long long t1 = (t0 + SPG_TC < T) ? t0 + SPG_TC : T;
-    float p = 0.0f;
-    for (long long t = t0; t < t1; t++) {
-        const float v = pwr(X[t * nfft + k]);
-        p = accum ? (1.0f - alpha) * p + alpha * v : p + v;
+    const long long nch = (T + SPG_TC - 1) / SPG_TC;
+    for (long long c = blockIdx.y; c < nch; c += gridDim.y) {   // chunks past LQ_GRID_Y_MAX: strided
+        const long long t0 = c * SPG_TC;
+        const long long t1 = (t0 + SPG_TC < T) ? t0 + SPG_TC : T;
+        float p = 0.0f;
+        for (long long t = t0; t < t1; t++) {
+            const float v = pwr(X[t * nfft + k]);
+            p = accum ? (1.0f - alpha) * p + alpha * v : p + v;
+        }
+        part[c * nfft + k] = p;
     }
-    part[(long long)blockIdx.y * nfft + k] = p;
 }
 
 // Folds chunk values part[c][k] (chunks of TC transforms, the last one
@@ -333,17 +341,22 @@ extern "C" void lqk_spgram_gather(int real_in, const void *hist, unsigned int W,
                                   unsigned long long T, const float *w, unsigned int nfft, void *out, void *stream)
 {
     if (T == 0) return;
-    const dim3 g((nfft + NT - 1) / NT, (unsigned)T);
+    const dim3 g((nfft + NT - 1) / NT, (unsigned)(T < LQ_GRID_Y_MAX ? T : LQ_GRID_Y_MAX));
     if (real_in)
         hipLaunchKernelGGL(k_spg_gather<float>, g, dim3(NT), 0, (hipStream_t)stream, (const float *)hist, (int)W,
-                           (const float *)x, ends, w, (int)nfft, (float2 *)out);
+                           (const float *)x, ends, (long long)T, w, (int)nfft, (float2 *)out);
     else
         hipLaunchKernelGGL(k_spg_gather<float2>, g, dim3(NT), 0, (hipStream_t)stream, (const float2 *)hist, (int)W,
-                           (const float2 *)x, ends, w, (int)nfft, (float2 *)out);
+                           (const float2 *)x, ends, (long long)T, w, (int)nfft, (float2 *)out);
     LQ_CHECK_LAUNCH();
 }
 
 constexpr long long SPG_G = 64;   // chunks per first-level fold group
+
+// the reduction's shape, for the tests: transforms per chunk, chunks per
+// first-level fold group
+extern "C" unsigned int lqk_spgram_chunk(void) { return SPG_TC; }
+extern "C" unsigned int lqk_spgram_fold_group(void) { return (unsigned)SPG_G; }
 
 extern "C" size_t lqk_spgram_work_bytes(unsigned long long T, unsigned int nfft)
 {
@@ -379,9 +392,11 @@ static void spg_reduce(const void *X, unsigned long long T, unsigned int nfft, i
                        void *work, void *stream)
 {
     if (T == 0) return;
-    const unsigned nch = (unsigned)((T + SPG_TC - 1) / SPG_TC);
+    const unsigned long long nch = (T + SPG_TC - 1) / SPG_TC;
     const unsigned gx = (nfft + NT - 1) / NT;
-    hipLaunchKernelGGL(k_spg_part, dim3(gx, nch), dim3(NT), 0, (hipStream_t)stream, (const float2 *)X, (long long)T,
+    // the chunks on grid.y up to LQ_GRID_Y_MAX; the kernel strides over the rest
+    const unsigned gy = (unsigned)(nch < LQ_GRID_Y_MAX ? nch : LQ_GRID_Y_MAX);
+    hipLaunchKernelGGL(k_spg_part, dim3(gx, gy), dim3(NT), 0, (hipStream_t)stream, (const float2 *)X, (long long)T,
                        (int)nfft, accum, alpha, (float *)work);
     LQ_CHECK_LAUNCH();
     spg_fold(T, nfft, accum, alpha, dst, work, (hipStream_t)stream);
@@ -399,6 +414,15 @@ extern "C" void lqk_spgram_sum(const void *X, unsigned long long T, unsigned int
     spg_reduce(X, T, nfft, 0, 0.0f, acc, work, stream);
 }
 
+// 0: gather, batch transform, k_spg_part; else the fused kernel, 1 + 2 HALF + 4 TR
+// (32-bit byte offsets into x: fewer than 2^27 samples per call)
+extern "C" int lqk_spgram_route(int real_in, unsigned int nfft, unsigned int W, unsigned long long n)
+{
+    if (nfft != 1024 || W > 1024 || n >= (1ull << 27)) return 0;
+    const int half = W <= 512;   // the zero half of each window is neither loaded nor weighted
+    return 1 + 2 * half + 4 * (half && !real_in);
+}
+
 extern "C" void lqk_spgram_fused1024(int real_in, const void *hist, unsigned int W, const void *x, long long e0,
                                      long long hop, unsigned long long T, long long elast, const float *w, int accum,
                                      float alpha, float *dst, void *work, void *stream)
@@ -407,17 +431,27 @@ extern "C" void lqk_spgram_fused1024(int real_in, const void *hist, unsigned int
     const unsigned nch = (unsigned)((T + SPG_TC - 1) / SPG_TC);
     const unsigned nwg = (nch + NT / 64 - 1) / (NT / 64);
     const float2 *tw = (const float2 *)lqrt_twiddles();
-    // W <= 512: the zero half of each window is neither loaded nor weighted
-    // (0.427-0.451 -> 0.410-0.424 ms per 2^26 inputs, identical output; r05zr)
-    const bool half = W <= 512;
+    // the instantiation is the route's code, 1 + 2 HALF + 4 TR.  HALF (W <= 512): the zero half
+    // of each window is neither loaded nor weighted (0.427-0.451 -> 0.410-0.424 ms per 2^26
+    // inputs, identical output; r05zr); TR: complex input only
+    const int r = lqk_spgram_route(real_in, 1024, W, 0);
+    bool ok;
     if (real_in)
-        hipLaunchKernelGGL((half ? k_spg_fused1024<float, true, false> : k_spg_fused1024<float, false, false>),
-                           dim3(nwg), dim3(NT), 0, (hipStream_t)stream, (const float *)hist, (int)W, (const float *)x,
-                           e0, hop, (long long)T, elast, w, accum, alpha, tw, (float *)work);
+        ok = lq_switch<1, 3>(r, [&](auto R) {
+            hipLaunchKernelGGL((k_spg_fused1024<float, (R & 2) != 0, (R & 4) != 0>), dim3(nwg), dim3(NT), 0,
+                               (hipStream_t)stream, (const float *)hist, (int)W, (const float *)x, e0, hop,
+                               (long long)T, elast, w, accum, alpha, tw, (float *)work);
+        });
     else
-        hipLaunchKernelGGL((half ? k_spg_fused1024<float2, true, true> : k_spg_fused1024<float2, false, false>),
-                           dim3(nwg), dim3(NT), 0, (hipStream_t)stream, (const float2 *)hist, (int)W,
-                           (const float2 *)x, e0, hop, (long long)T, elast, w, accum, alpha, tw, (float *)work);
+        ok = lq_switch<1, 7>(r, [&](auto R) {
+            hipLaunchKernelGGL((k_spg_fused1024<float2, (R & 2) != 0, (R & 4) != 0>), dim3(nwg), dim3(NT), 0,
+                               (hipStream_t)stream, (const float2 *)hist, (int)W, (const float2 *)x, e0, hop,
+                               (long long)T, elast, w, accum, alpha, tw, (float *)work);
+        });
+    if (!ok) {
+        fprintf(stderr, "error: liquid-mi355x: spgram route %d has no fused kernel (W = %u)\n", r, W);
+        exit(1);
+    }
     LQ_CHECK_LAUNCH();
     spg_fold(T, 1024, accum, alpha, dst, work, (hipStream_t)stream);
 }

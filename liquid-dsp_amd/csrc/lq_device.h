@@ -16,6 +16,11 @@ void lq_check(hipError_t e, const char *what, const char *file, int line);
 
 #define LQ_TW_N 4096
 
+// The most workgroups a launch puts on grid.y (what every HIP device accepts,
+// whatever maxGridSize[1] reports): kernels that carry a batch there stride
+// over the rest, for (z = blockIdx.y; z < batch; z += gridDim.y).
+#define LQ_GRID_Y_MAX 65535ull
+
 // Host-side dispatch of a runtime value to a template argument: calls
 // f(std::integral_constant<int, V>{}) for the V in Vs... equal to v and
 // returns true; false (nothing called) if there is none.  The list is the

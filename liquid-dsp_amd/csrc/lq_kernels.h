@@ -321,6 +321,34 @@ void lqk_firpfb_single(int kind, const void *hpoly, unsigned int L, unsigned int
 size_t lqk_fft_work_bytes(unsigned int n, unsigned long long batch);
 void lqk_fft_any(unsigned int n, int dir, const void *x, void *y, unsigned long long batch, void *work,
                  void *stream);
+/* The kernels lqk_fft_any takes for n points read from a pointer that is or is
+ * not 16-byte aligned -- the decision the launches themselves switch on
+ * (lq_fft_batch_scaled, fft_four_step, lqk_fft_any).  a16: the 16-byte loads of
+ * the 8192- and 16384-point kernels; N1 x N2: the two-pass split of n
+ * (FOUR_STEP) or of M (BLUESTEIN_FUSED), columns k_fft2p_cols_r / k_bs_cols_r
+ * <N1 / 256>, rows k_bs_rows_s<N2 / 16> when rows_s, else k_fft2p_rows_r /
+ * k_bs_rows_r<N2 / 256>; M: Bluestein's padded size (its M-point transforms go
+ * by lqk_fft_route(M) when not fused). */
+enum {
+    LQK_FFT_REFUSED = 0,          /* n = 0 or past 2^24 (2^23 when not a power of two) */
+    LQK_FFT_DFT = 1,              /* k_dft_batch: n = 1 and other n <= 16 */
+    LQK_FFT_BATCH = 2,            /* k_fft_batch<n>: 2, 4, 8, 16 */
+    LQK_FFT_SMALL = 3,            /* k_fftsmall_batch<n / 16>: 32, 64, 128 */
+    LQK_FFT_R16 = 4,              /* k_fftr16_batch<n / 256>: 256, 512, 2048 */
+    LQK_FFT_1024 = 5,
+    LQK_FFT_4096 = 6,
+    LQK_FFT_8192 = 7,
+    LQK_FFT_16384 = 8,
+    LQK_FFT_FOUR_STEP = 9,        /* powers of two from 32768 */
+    LQK_FFT_BLUESTEIN = 10,       /* M <= 4096: k_bs_pre, M-point transform, k_bs_mul, back, k_bs_post */
+    LQK_FFT_BLUESTEIN_FUSED = 11, /* M > 4096: chirp products fused into the two-pass kernels */
+};
+typedef struct {
+    int family, a16, rows_s;
+    unsigned int N1, N2;
+    unsigned long long M;
+} lqk_fft_route_t;
+lqk_fft_route_t lqk_fft_route(unsigned int n, int aligned16);
 /* real-to-real (fft_r2r_1d.c): type codes as liquid_fft_type (10-13 DCT, 20-23 DST); x must not alias y */
 enum {
     LQK_R2R_REDFT00 = 10, LQK_R2R_REDFT10 = 11, LQK_R2R_REDFT01 = 12, LQK_R2R_REDFT11 = 13,
@@ -345,6 +373,12 @@ void lqk_spgram_sum(const void *X, unsigned long long T, unsigned int nfft, floa
 void lqk_spgram_fused1024(int real_in, const void *hist, unsigned int W, const void *x, long long e0,
                           long long hop, unsigned long long T, long long elast, const float *w, int accum,
                           float alpha, float *dst, void *work, void *stream);
+/* the launches' own decisions, for the tests: the path of a call of n samples (0: gather, batch
+ * transform, k_spg_part; else k_spg_fused1024<S, HALF, TR> as 1 + 2 HALF + 4 TR), the transforms
+ * per chunk and the chunks per first-level fold group (more chunks fold in two levels) */
+int lqk_spgram_route(int real_in, unsigned int nfft, unsigned int W, unsigned long long n);
+unsigned int lqk_spgram_chunk(void);
+unsigned int lqk_spgram_fold_group(void);
 void lqk_spgram_db(int mode, const void *X, const float *v, unsigned int nfft, float T, float *out, void *stream);
 
 /* ---------------------------------------------------------------- resamp2 (half-band)

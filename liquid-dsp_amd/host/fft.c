@@ -149,3 +149,28 @@ unsigned int liquid_nextpow2(unsigned int _x)
     }
     return n;
 }
+
+/* include/liquid_mi355x.h: the launch's own decision, packed */
+#define LQ_SAME_FAMILY(NAME) _Static_assert((int)LIQUID_MI355X_FFT_##NAME == (int)LQK_FFT_##NAME, "fft route: " #NAME)
+LQ_SAME_FAMILY(REFUSED);
+LQ_SAME_FAMILY(DFT);
+LQ_SAME_FAMILY(BATCH);
+LQ_SAME_FAMILY(SMALL);
+LQ_SAME_FAMILY(R16);
+LQ_SAME_FAMILY(1024);
+LQ_SAME_FAMILY(4096);
+LQ_SAME_FAMILY(8192);
+LQ_SAME_FAMILY(16384);
+LQ_SAME_FAMILY(FOUR_STEP);
+LQ_SAME_FAMILY(BLUESTEIN);
+LQ_SAME_FAMILY(BLUESTEIN_FUSED);
+#undef LQ_SAME_FAMILY
+int liquid_mi355x_fft_route(unsigned int _n, int _aligned16)
+{
+    const lqk_fft_route_t r = lqk_fft_route(_n, _aligned16);
+    int lg1 = 0, lg2 = 0, lgm = 0;
+    while ((1u << lg1) < r.N1) lg1++;
+    while ((1u << lg2) < r.N2) lg2++;
+    while ((1ull << lgm) < r.M) lgm++;
+    return r.family | (r.a16 ? 16 : 0) | (r.rows_s ? 32 : 0) | (lg1 << 8) | (lg2 << 16) | (lgm << 24);
+}

@@ -195,7 +195,7 @@ static void lq_spg_accumulate_dev(lq_spg *q, const void *dx, unsigned long long 
     if (H > 0) {   /* transform after the input that brings sample_counter to W/2 */
         const long long first = (long long)(H - q->sample_counter) - 1;
         if (first < (long long)n) T = (unsigned long long)(((long long)n - 1 - first) / H + 1);
-        if (q->nfft == 1024 && n < (1ull << 27)) {   /* fused path: ends are first + t H, no table */
+        if (lqk_spgram_route(q->real_in, q->nfft, q->W, n)) {   /* fused path: ends are first + t H, no table */
             if (T > 0) {
                 float a = q->num_transforms == 0 ? 1.0f : alpha;
                 void *w = lq_devbuf_get(&q->work, lqk_spgram_work_bytes(T, q->nfft));
@@ -250,7 +250,7 @@ static void lq_spg_estimate_dev(lq_spg *q, const void *dx, unsigned long long n,
     unsigned long long T = n / delay + ((n % delay) ? 1 : 0);
     float *acc = (float *)lq_devbuf_get(&q->acc, q->nfft * sizeof(float));
     lqrt_memset(acc, q->nfft * sizeof(float), q->ctx.stream);
-    if (q->nfft == 1024 && n < (1ull << 27)) {   /* fused path: ends are delay-1 + t delay, the last one n-1 */
+    if (lqk_spgram_route(q->real_in, q->nfft, q->W, n)) {   /* fused path: ends are delay-1 + t delay, the last one n-1 */
         void *w = lq_devbuf_get(&q->work, lqk_spgram_work_bytes(T, q->nfft));
         lqk_spgram_fused1024(q->real_in, lq_spg_win(q), q->W, dx, (long long)delay - 1, (long long)delay, T,
                              (long long)n - 1, q->d_w, 0, 0.0f, acc, w, q->ctx.stream);
@@ -345,3 +345,12 @@ static void lq_spg_estimate(lq_spg *q, const void *x, unsigned int n, float *psd
 
 LQ_SPGRAM_FRONT(spgramcf, 0, liquid_float_complex)
 LQ_SPGRAM_FRONT(spgramf, 1, float)
+
+/* the reduction's shape and the path of a call, as the launches decide them (include/liquid_mi355x.h) */
+int liquid_mi355x_spgram_route(int _real_in, unsigned int _nfft, unsigned int _window_len, unsigned long long _n)
+{
+    return lqk_spgram_route(_real_in, _nfft, _window_len, _n);
+}
+unsigned int liquid_mi355x_spgram_chunk(void) { return lqk_spgram_chunk(); }
+unsigned int liquid_mi355x_spgram_fold_group(void) { return lqk_spgram_fold_group(); }
+unsigned long long liquid_mi355x_spgram_batch_samples(void) { return SPG_MAX_BATCH_SAMPLES; }

@@ -109,6 +109,62 @@ def fftfilt_nfft(t, hlen):
     return int(fn(1 if t == RRRF else 0, hlen))
 
 
+# liquid_mi355x_fft_route's families, by name
+FFT_FAMILIES = ("refused", "dft", "k_fft_batch", "fftsmall", "fftr16", "fft1024", "fft4096", "fft8192", "fft16384",
+                "four_step", "bluestein", "bluestein_fused")
+
+
+def fft_route(n, aligned16=True):
+    """The kernels an FFT plan of n points takes (no GPU call), by name, from
+    the launch's own decision: "dft", "k_fft_batch<8>", "fftsmall<4>",
+    "fftr16<2>", "fft1024", "fft4096", "fft8192/a16", "fft8192/a8",
+    "four_step 256x128 cols_r<1> rows_s<8>", "bluestein M=64",
+    "bluestein_fused M=8192 128x64 cols_s<8> rows_s<4>", "refused"."""
+    r = int(lib().liquid_mi355x_fft_route(n, 1 if aligned16 else 0))
+    fam = FFT_FAMILIES[r & 15]
+    N1, N2, M = 1 << ((r >> 8) & 31), 1 << ((r >> 16) & 31), 1 << ((r >> 24) & 31)
+    if fam == "k_fft_batch":
+        return "k_fft_batch<%d>" % n
+    if fam == "fftsmall":
+        return "fftsmall<%d>" % (n // 16)
+    if fam == "fftr16":
+        return "fftr16<%d>" % (n // 256)
+    if fam in ("fft8192", "fft16384"):
+        return fam + ("/a16" if r & 16 else "/a8")
+    if fam in ("four_step", "bluestein_fused"):
+        cols = "cols_r<%d>" % (N1 // 256) if N1 >= 256 else "cols_s<%d>" % (N1 // 16)
+        rows = "rows_s<%d>" % (N2 // 16) if r & 32 else "rows_r<%d>" % (N2 // 256)
+        return "%s%s %dx%d %s %s" % (fam, " M=%d" % M if fam == "bluestein_fused" else "", N1, N2, cols, rows)
+    if fam == "bluestein":
+        return "bluestein M=%d" % M
+    return fam
+
+
+def spgram_route(real_in, nfft, W, n=1):
+    """The path of a spgram call of n samples (no GPU call): "plain" (gather,
+    batch transform, k_spg_part) or the fused kernel's instantiation,
+    "fused<float2,HALF,TR>" ..."""
+    r = int(lib().liquid_mi355x_spgram_route(1 if real_in else 0, nfft, W, n))
+    if r == 0:
+        return "plain"
+    return "fused<%s,%s,%s>" % ("float" if real_in else "float2", "HALF" if r & 2 else "full", "TR" if r & 4 else "lds")
+
+
+def spgram_chunk():
+    """Transforms per chunk of spgram's per-bin reduction (SPG_TC)."""
+    return int(lib().liquid_mi355x_spgram_chunk())
+
+
+def spgram_fold_group():
+    """Chunks per first-level fold group; more chunks than this fold in two levels."""
+    return int(lib().liquid_mi355x_spgram_fold_group())
+
+
+def spgram_batch_samples():
+    """Samples (transforms x nfft) per launch batch of the plain path."""
+    return int(lib().liquid_mi355x_spgram_batch_samples())
+
+
 # liquid_mi355x_resamp_route's and liquid_mi355x_resamp2_route's codes, by name
 RESAMP_ROUTES = ("resamp3/const", "resamp3/stride", "resamp/", "generic/", "resamp4/up", "resamp4/up_r4",
                  "resamp4/down", "resamp4/down_dn")
@@ -513,6 +569,11 @@ def _declare(L):
         "liquid_mi355x_firdecim_grid_cap": (u, [i, u, u, i]),
         "liquid_mi355x_firinterp_route": (i, [i, u, u, i]),
         "liquid_mi355x_firinterp_max_taps": (u, [i]),
+        "liquid_mi355x_fft_route": (i, [u, i]),
+        "liquid_mi355x_spgram_route": (i, [i, u, u, ull]),
+        "liquid_mi355x_spgram_chunk": (u, []),
+        "liquid_mi355x_spgram_fold_group": (u, []),
+        "liquid_mi355x_spgram_batch_samples": (ull, []),
         "liquid_mi355x_resamp_route": (i, [i, f, u, u, ull, vp]),
         "liquid_mi355x_resamp2_route": (i, [i, u, ull, vp]),
         "liquid_mi355x_msresamp_route": (i, [i, f, f, ull, vp, vp]),
@@ -1879,3 +1940,14 @@ class Spgram(_Obj):
         X = np.zeros(self.nfft, np.float32)
         self._fn("_estimate_psd")(self.q, ptr(x), len(x), ptr(X))
         return X
+
+    def accumulate_psd_dev(self, dx, n, alpha):
+        """n samples at the device address dx"""
+        self._fn("_accumulate_psd_dev")(self.q, dx, alpha, n)
+
+    def estimate_psd_dev(self, dx, n, dpsd):
+        """n samples at the device address dx; nfft floats (dB, shifted) to the device address dpsd"""
+        self._fn("_estimate_psd_dev")(self.q, dx, n, dpsd)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
