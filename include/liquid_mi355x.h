@@ -594,6 +594,11 @@ void liquid_cplxpair_cleanup(liquid_float_complex *_p, unsigned int _n, unsigned
 unsigned int liquid_mi355x_iirfilt_run(void);
 unsigned int liquid_mi355x_iirfilt_tile(void);
 unsigned int liquid_mi355x_iirfilt_scan(void);
+/* extension: the launches a device call of _n full-rate samples takes (no GPU
+   call): 0 the apply stage alone (at most one tile), 1 one scan launch
+   between the tile and apply stages (at most scan tiles), 2 three scan
+   launches (reduce per chunk, scan the chunk totals, scan within the chunks) */
+int liquid_mi355x_iirfilt_route(unsigned long long _n);
 
 /* ------------------------------------------------------------------------ */
 /* iirdecim (liquid.h:2738-2820), iirinterp (liquid.h:2570-2650)             */

@@ -445,7 +445,8 @@ void run_piece(unsigned int nsec, const void *coef_, const void *lad_, void *sta
     const S *x = (const S *)x_;
     const int vec = (((MODE == INTERP ? 0 : (uintptr_t)x_) | (MODE == DECIM ? 0 : (uintptr_t)y_)) & 15) == 0;
     const long long ntiles = (long long)((n + TILE - 1) / TILE);
-    if (ntiles == 1) {
+    const int route = lqk_iirfilt_route(n);
+    if (route == 0) {
         hipLaunchKernelGGL((k_iir_apply<KIND, MS, MODE>), dim3(1), dim3(NT), 0, st, coef, (int)nsec, lad, x,
                            (long long)n, vec, (const S *)state, 0, y, state, M);
         LQ_CHECK_LAUNCH();
@@ -456,7 +457,7 @@ void run_piece(unsigned int nsec, const void *coef_, const void *lad_, void *sta
     hipLaunchKernelGGL((k_iir_tile<KIND, MS, MODE == INTERP ? INTERP : PLAIN>), dim3((unsigned)(ntiles - 1)), dim3(NT),
                        0, st, coef, (int)nsec, lad, x, vec, z, M);
     LQ_CHECK_LAUNCH();
-    if (nch == 1) {
+    if (route == 1) {
         hipLaunchKernelGGL((k_iir_scan<KIND, MS>), dim3(1), dim3(NT), 0, st, lad + LV_SCAN * PM * PM, (int)nsec,
                            (const S *)z, ntiles - 1, (const S *)state, start, ntiles, (S *)nullptr);
         LQ_CHECK_LAUNCH();
@@ -506,6 +507,17 @@ extern "C" unsigned int lqk_iirfilt_maxsec(unsigned int nsec)
     unsigned int ms = 1;
     while (ms < nsec) ms *= 2;
     return ms;
+}
+
+// the launch structure of a piece of n full-rate samples (a longer call: of
+// its full pieces): 0 k_iir_apply alone, 1 one k_iir_scan launch between the
+// tile and apply stages, 2 three (reduce per chunk / scan the chunk totals /
+// scan within the chunks)
+extern "C" int lqk_iirfilt_route(unsigned long long n)
+{
+    if (n > PIECE) n = PIECE;
+    const unsigned long long ntiles = (n + TILE - 1) / TILE;
+    return ntiles <= 1 ? 0 : ntiles <= NT ? 1 : 2;
 }
 
 extern "C" size_t lqk_iirfilt_work_bytes(int kind, unsigned int nsec, unsigned long long n)

@@ -435,6 +435,9 @@ void lqk_firhilb_c2r(const void *x, unsigned long long n, void *y, void *stream)
 #define LQK_IIRFILT_LEVELS 23
 unsigned int lqk_iirfilt_maxsec(unsigned int nsec);
 size_t lqk_iirfilt_work_bytes(int kind, unsigned int nsec, unsigned long long n);
+/* launches of a piece of n full-rate samples: 0 apply alone (at most one tile), 1 one scan launch (at
+ * most LQK_IIRFILT_SCAN tiles), 2 three scan launches */
+int lqk_iirfilt_route(unsigned long long n);
 void lqk_iirfilt(int kind, unsigned int nsec, const void *coef, const void *ladder, void *state, const void *x,
                  unsigned long long n, void *y, void *work, void *stream);
 /* The same filter as a rate changer by M, 1 <= M <= LQK_IIRFILT_TILE, with the

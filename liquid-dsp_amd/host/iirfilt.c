@@ -757,10 +757,12 @@ void lq_iir_run_rate_dev(lq_iir *q, int mode, unsigned int M, const void *dx, un
     iir_rate_dev(q, mode, M, dx, n, dy);
 }
 
-/* block geometry of the device path (tests cut streams at these) */
+/* block geometry of the device path (tests cut streams at these) and the
+ * launch structure a call of n full-rate samples takes (lqk_iirfilt_route) */
 unsigned int liquid_mi355x_iirfilt_run(void) { return LQK_IIRFILT_RUN; }
 unsigned int liquid_mi355x_iirfilt_tile(void) { return LQK_IIRFILT_TILE; }
 unsigned int liquid_mi355x_iirfilt_scan(void) { return LQK_IIRFILT_SCAN; }
+int liquid_mi355x_iirfilt_route(unsigned long long _n) { return lqk_iirfilt_route(_n); }
 
 /* ------------------------------------------------------------------ typed front ends */
 #define LQ_IIRFILT_DEFINE(IIRFILT, KIND, TO, TC, TI)                                                          \

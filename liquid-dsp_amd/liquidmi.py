@@ -150,6 +150,17 @@ def spgram_route(real_in, nfft, W, n=1):
     return "fused<%s,%s,%s>" % ("float" if real_in else "float2", "HALF" if r & 2 else "full", "TR" if r & 4 else "lds")
 
 
+# liquid_mi355x_iirfilt_route's codes, by name
+IIRFILT_ROUTES = ("apply", "scan1", "scan3")
+
+
+def iirfilt_route(n):
+    """The launches of an iirfilt / iirdecim / iirinterp device call of n
+    full-rate samples (no GPU call): "apply" (k_iir_apply alone), "scan1" (one
+    k_iir_scan launch) or "scan3" (three)."""
+    return IIRFILT_ROUTES[lib().liquid_mi355x_iirfilt_route(n)]
+
+
 def spgram_chunk():
     """Transforms per chunk of spgram's per-bin reduction (SPG_TC)."""
     return int(lib().liquid_mi355x_spgram_chunk())
@@ -471,6 +482,7 @@ def _declare(L):
         "liquid_mi355x_iirfilt_run": (u, []),
         "liquid_mi355x_iirfilt_tile": (u, []),
         "liquid_mi355x_iirfilt_scan": (u, []),
+        "liquid_mi355x_iirfilt_route": (i, [ull]),
     })
     for t in (CCCF, RRRF):
         sig.update({
