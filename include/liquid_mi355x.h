@@ -692,6 +692,69 @@ unsigned int liquid_mi355x_autocorr_tile(void);
 unsigned int liquid_mi355x_autocorr_max_window(void);
 
 /* ------------------------------------------------------------------------ */
+/* detector_cccf (liquid.h:4117-4152): preamble correlator bank              */
+/* ------------------------------------------------------------------------ */
+/* Cross-correlates the stream against the sequence s (n samples) in a bank of
+   m frequency-shifted copies, m = max(2, ceil(|dphi_max / dphi_step|)),
+   dphi_step = 0.8 pi / n, template k = conj(s[i]) exp(-j dphi[k] i) with
+   dphi[k] = (k - (m-1)/2) dphi_step.  For stream sample t (counted from the
+   last reset, zeros before it) and its window w_t = x[t-n+1 .. t]:
+     r_k[t] = |sum_i p_k[i] w_t[i]| / sqrt(n E[t]),   E[t] = sum_i |w_t[i]|^2,
+   and correlate() runs the reference's SEEK / FINDMAX state machine over the
+   rows r[t] (detector_cccf.c:247-330), returning 1 at the sample after a peak
+   with the timing, carrier and gain estimates (:396-454).
+   Where this differs from the reference: (1) E[t] is the float32 sum of its
+   own window, not the reference's running add-and-subtract, whose rounding
+   error grows over the life of the stream; (2) where E[t] = 0 every r_k[t] is
+   exactly 0 (the reference divides 0 by 0; its NaN compares above nothing, so
+   the decisions are the same); (3) reset zeroes all three stored rows (the
+   reference leaves the newest as it was).
+   correlate() runs on the host and needs no GPU; the block calls need one at
+   their first use.  Per-sample and block calls share one state and may follow
+   each other in any order.
+   Extensions: correlate_block reports every detection correlate() would have
+   reported over _x[0.._n): it returns their number and writes the first
+   _max_det of them -- _index (offset in this call of the sample at which
+   correlate returns 1), _tau_hat, _dphi_hat, _gamma_hat; any of the four
+   arrays may be NULL.  correlate_block_dev takes _dx in device memory; _drxy
+   is NULL or _n*m floats in device memory, row t = r_0[t] .. r_{m-1}[t],
+   formed for every sample whether the detector's timer runs or not.  The
+   detections come back in host arrays, so correlate_block_dev synchronises
+   the object's stream before it returns.  device_eligible: block calls run on
+   the GPU (n <= liquid_mi355x_detector_max_len() and m <=
+   liquid_mi355x_detector_max_correlators()), else in a host loop.
+   get_templates copies the m*n template values as held (row k = p_k). */
+typedef struct detector_cccf_s *detector_cccf;
+detector_cccf detector_cccf_create(liquid_float_complex *_s, unsigned int _n, float _threshold, float _dphi_max);
+void detector_cccf_destroy(detector_cccf _q);
+void detector_cccf_print(detector_cccf _q);
+void detector_cccf_reset(detector_cccf _q);
+int detector_cccf_correlate(detector_cccf _q, liquid_float_complex _x, float *_tau_hat, float *_dphi_hat,
+                            float *_gamma_hat);
+unsigned int detector_cccf_correlate_block(detector_cccf _q, liquid_float_complex *_x, unsigned int _n,
+                                           unsigned int *_index, float *_tau_hat, float *_dphi_hat,
+                                           float *_gamma_hat, unsigned int _max_det);
+unsigned int detector_cccf_correlate_block_dev(detector_cccf _q, const liquid_float_complex *_dx,
+                                               unsigned long long _n, float *_drxy, unsigned long long *_index,
+                                               float *_tau_hat, float *_dphi_hat, float *_gamma_hat,
+                                               unsigned int _max_det);
+unsigned int detector_cccf_get_num_correlators(detector_cccf _q);
+void detector_cccf_get_templates(detector_cccf _q, liquid_float_complex *_p);
+int detector_cccf_device_eligible(detector_cccf _q);
+void detector_cccf_set_stream(detector_cccf _q, void *_hip_stream);
+void detector_cccf_synchronize(detector_cccf _q);
+
+/* extension: outputs per workgroup of the block kernel, the longest sequence
+   and the widest bank it takes */
+unsigned int liquid_mi355x_detector_tile(void);
+unsigned int liquid_mi355x_detector_max_len(void);
+unsigned int liquid_mi355x_detector_max_correlators(void);
+/* tests only: records the block call's device list holds (0: the default);
+   a call that marks more samples than that runs in pieces, with the same
+   result */
+void liquid_mi355x_detector_set_list_capacity(unsigned int _records);
+
+/* ------------------------------------------------------------------------ */
 /* fftfilt (liquid.h:2192-2240): rrrf, crcf, cccf                            */
 /* ------------------------------------------------------------------------ */
 #define LQMI_FFTFILT_API(FFTFILT, TO, TC, TI)                                                   \

@@ -522,6 +522,36 @@ void lqk_freqmod(float ref, const void *tab, const unsigned *acc_in, unsigned *a
 void lqk_freqdem(float ref, unsigned M, const void *hist, void *hist_out, const void *r, float *m,
                  unsigned long long n, void *stream);
 
+/* ---------------------------------------------------------------- detector (k_detector.hip)
+ * The correlator bank of detector_cccf over the stream s = hist ++ x (hist:
+ * the len samples before x, oldest first; hist_new receives the last len of s
+ * and must not alias hist).  For sample t < n with window w = s[t-len+1 .. t]:
+ *   c_k = sum_i p_k[i] w[i], E = sum_i |w[i]|^2, r_k = |c_k| / sqrt(len E)
+ * (0 where E == 0), each a float32 sum of its own window, i = 0 .. len-1 in
+ * order.  pt: the templates tap-major and zero padded, pt[i * m + k] = p_k[i]
+ * for i < len, 0 for len <= i < LQK_DETECTOR_PADLEN(len), complex, 16-byte
+ * aligned device memory.  drxy: NULL or n * m floats, row t = r_0 .. r_{m-1}.
+ * With nt = ceil(n / LQK_DETECTOR_TILE) tiles, list is device memory of
+ * LQK_DETECTOR_LIST_WORDS(m, nt, cap) 32-bit words: word 0 is the number of
+ * marked samples (zeroed by the launch itself before the kernel); from word
+ * LQK_DETECTOR_LIST_HEAD on, one word of flags per tile (bit 0 / 2: the largest
+ * r_k of the tile's first / last sample exceeds thr; bit 1 / 3: that sample is
+ * marked); then the first cap records of 2 + m words each, in no particular
+ * order: t, E, r_0 .. r_{m-1}.  Marked: the samples whose largest r_k exceeds
+ * thr, the samples next to one in the same tile, and the first and last sample
+ * of the call.  edge: device memory, 2 nt records of the same form: the first
+ * and the last sample of every tile.  1 <= len <= LQK_DETECTOR_MAXLEN, 2 <= m
+ * <= LQK_DETECTOR_MAXM, n < 2^31. */
+#define LQK_DETECTOR_TILE 2048
+#define LQK_DETECTOR_MAXLEN 2048
+#define LQK_DETECTOR_MAXM 16
+#define LQK_DETECTOR_LIST_HEAD 4
+#define LQK_DETECTOR_PADLEN(len) (((len) + 3u) & ~3u)
+#define LQK_DETECTOR_LIST_WORDS(m, nt, cap) (LQK_DETECTOR_LIST_HEAD + (size_t)(nt) + (size_t)(cap) * (2u + (m)))
+void lqk_detector(unsigned int len, unsigned int m, float thr, const void *pt, const void *hist, const void *x,
+                  unsigned long long n, float *drxy, unsigned int *list, unsigned int cap, unsigned int *edge,
+                  void *hist_new, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

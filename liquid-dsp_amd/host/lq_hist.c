@@ -15,17 +15,35 @@ void lq_hist_init(lq_hist *h, size_t n, size_t esz, int mode)
     if (mode != LQ_HIST_DEV) lq_mirror_init(&h->m, n, esz, mode == LQ_HIST_PINNED);
 }
 
+void lq_hist_init_host(lq_hist *h, size_t n, size_t esz)
+{
+    memset(h, 0, sizeof(*h));
+    h->mode = LQ_HIST_MIRROR;
+    lq_mirror_init(&h->m, n, esz, 0);
+}
+
+void lq_hist_attach(lq_hist *h)
+{
+    if (h->d[0]) return;
+    for (int i = 0; i < 2; i++) h->d[i] = lqrt_malloc((h->m.n ? h->m.n : 1) * h->m.esz);
+    h->m.dev_valid = 0;   /* the mirror is authoritative */
+}
+
 void lq_hist_free(lq_hist *h)
 {
-    lqrt_free(h->d[0]);
-    lqrt_free(h->d[1]);
+    if (h->d[0]) {
+        lqrt_free(h->d[0]);
+        lqrt_free(h->d[1]);
+    }
     if (h->mode != LQ_HIST_DEV) lq_mirror_free(&h->m);
 }
 
 void lq_hist_zero(lq_hist *h, void *stream)
 {
-    for (int i = 0; i < 2; i++) lqrt_memset(h->d[i], h->m.n * h->m.esz, stream);
-    lqrt_sync(stream);
+    if (h->d[0]) {
+        for (int i = 0; i < 2; i++) lqrt_memset(h->d[i], h->m.n * h->m.esz, stream);
+        lqrt_sync(stream);
+    }
     if (h->mode != LQ_HIST_DEV) lq_mirror_zero(&h->m);
 }
 

@@ -133,6 +133,11 @@ typedef struct {
     lq_mirror m;
 } lq_hist;
 void lq_hist_init(lq_hist *h, size_t n, size_t esz, int mode);
+/* an object whose per-sample calls need no GPU: MIRROR mode with the host side
+ * only (no runtime call); lq_hist_attach, before the first device use, adds
+ * the device pair (once; the mirror stays authoritative) */
+void lq_hist_init_host(lq_hist *h, size_t n, size_t esz);
+void lq_hist_attach(lq_hist *h);
 void lq_hist_free(lq_hist *h);
 void lq_hist_zero(lq_hist *h, void *stream);   /* both sides zero and in step; waits for the stream */
 void *lq_hist_dev(lq_hist *h, void *stream);   /* the current device buffer, brought up to date */

@@ -502,6 +502,22 @@ def _declare(L):
     sig.update({
         "liquid_mi355x_autocorr_tile": (u, []),
         "liquid_mi355x_autocorr_max_window": (u, []),
+        "detector_cccf_create": (vp, [vp, u, f, f]),
+        "detector_cccf_destroy": (None, [vp]),
+        "detector_cccf_print": (None, [vp]),
+        "detector_cccf_reset": (None, [vp]),
+        "detector_cccf_correlate": (i, [vp, cfloat, vp, vp, vp]),
+        "detector_cccf_correlate_block": (u, [vp, vp, u, vp, vp, vp, vp, u]),
+        "detector_cccf_correlate_block_dev": (u, [vp, vp, ull, vp, vp, vp, vp, vp, u]),
+        "detector_cccf_get_num_correlators": (u, [vp]),
+        "detector_cccf_get_templates": (None, [vp, vp]),
+        "detector_cccf_device_eligible": (i, [vp]),
+        "detector_cccf_set_stream": (None, [vp, vp]),
+        "detector_cccf_synchronize": (None, [vp]),
+        "liquid_mi355x_detector_tile": (u, []),
+        "liquid_mi355x_detector_max_len": (u, []),
+        "liquid_mi355x_detector_max_correlators": (u, []),
+        "liquid_mi355x_detector_set_list_capacity": (None, [u]),
     })
     sig.update({
         "nco_crcf_create": (vp, [i]),
@@ -1396,6 +1412,80 @@ class AutoCorr(_Obj):
 
     def get_energy(self):
         return float(self._fn("_get_energy")(self.q))
+
+
+def set_detector_list_capacity(records):
+    """Records the detector's device list holds (0: the default).  For tests."""
+    lib().liquid_mi355x_detector_set_list_capacity(int(records))
+
+
+class Detector(_Obj):
+    """detector_cccf: preamble correlator bank over the sequence s.  correlate()
+    runs on the host (the constructor needs no GPU); the block calls run on the
+    GPU when device_eligible, else in the library's host loop.  A detection is
+    (index, tau_hat, dphi_hat, gamma_hat); the block calls return (count,
+    index, tau_hat, dphi_hat, gamma_hat) with arrays of min(count, max_det)."""
+    prefix = "detector_cccf"
+    TILE = _LibConst("liquid_mi355x_detector_tile")                         # outputs per workgroup
+    MAX_LEN = _LibConst("liquid_mi355x_detector_max_len")                   # the longest sequence the kernel takes
+    MAX_CORRELATORS = _LibConst("liquid_mi355x_detector_max_correlators")   # the widest bank it takes
+
+    def __init__(self, s, threshold, dphi_max):
+        self.s = _samples(s, CCCF)
+        self.n = len(self.s)
+        self.q = self._fn("_create")(ptr(self.s), self.n, float(threshold), float(dphi_max))
+
+    @property
+    def device_eligible(self):
+        return bool(self._fn("_device_eligible")(self.q))
+
+    @property
+    def num_correlators(self):
+        return int(self._fn("_get_num_correlators")(self.q))
+
+    def templates(self):
+        """the m x n template values as the library holds them"""
+        p = np.zeros((self.num_correlators, self.n), np.complex64)
+        self._fn("_get_templates")(self.q, ptr(p))
+        return p
+
+    def reset(self):
+        self._fn("_reset")(self.q)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
+
+    def correlate(self, v):
+        """one sample: None, or (tau_hat, dphi_hat, gamma_hat) at a detection"""
+        e = np.zeros(3, np.float32)
+        if self._fn("_correlate")(self.q, _by_value(v, CCCF), ptr(e[0:]), ptr(e[1:]), ptr(e[2:])):
+            return e[0], e[1], e[2]
+        return None
+
+    @staticmethod
+    def _outputs(max_det, index_dtype, guard):
+        idx = np.full(max_det + guard, np.iinfo(index_dtype).max, index_dtype)
+        est = [np.full(max_det + guard, np.float32(-77.0)) for _ in range(3)]
+        return idx, est
+
+    def correlate_block(self, x, max_det=64, guard=0):
+        """host pointers; guard: extra entries left after max_det, returned
+        untouched (for tests of max_det)"""
+        x = _samples(x, CCCF)
+        idx, est = self._outputs(max_det, np.uint32, guard)
+        cnt = int(self._fn("_correlate_block")(self.q, ptr(x), len(x), ptr(idx), ptr(est[0]), ptr(est[1]),
+                                               ptr(est[2]), max_det))
+        k = len(idx) if guard else min(cnt, max_det)
+        return cnt, idx[:k], est[0][:k], est[1][:k], est[2][:k]
+
+    def correlate_block_dev(self, dx, n, drxy=0, max_det=64):
+        """dx: n samples in device memory; drxy: 0 or n * m floats in device
+        memory.  Waits for the object's stream."""
+        idx, est = self._outputs(max_det, np.uint64, 0)
+        cnt = int(self._fn("_correlate_block_dev")(self.q, dx, n, drxy or None, ptr(idx), ptr(est[0]), ptr(est[1]),
+                                                   ptr(est[2]), max_det))
+        k = min(cnt, max_det)
+        return cnt, idx[:k], est[0][:k], est[1][:k], est[2][:k]
 
 
 LIQUID_NCO, LIQUID_VCO = 0, 1

@@ -8,6 +8,7 @@ GB/s (bytes stated per workload) as a fraction of the 8 TB/s spec.
     python tools/bench_widened.py --halfband      (the resamp2 / firhilbf / msresamp rows alone)
     python tools/bench_widened.py --iir           (the iirfilt, iirdecim and iirinterp rows alone)
     python tools/bench_widened.py --autocorr      (the autocorr rows alone)
+    python tools/bench_widened.py --detector      (the detector_cccf rows alone)
 """
 import json
 import os
@@ -239,8 +240,106 @@ def autocorr_rows(L):
     sys.stdout.flush()
 
 
+def detector_rows(L):
+    """detector_cccf, 2^24 samples of noise in device memory (nothing crosses the threshold: the decision
+    pass sees the call's first and last sample and one word of flags per tile), (n, m) = (64, 2), (256, 4), (1341, 11) and (512, 16: a bank the
+    kernel walks in two halves), without and with the rows in drxy.  A call returns its detections in host memory, so the time of a call (events around
+    synchronous calls) holds the kernel, the copy of the marked list and the host pass; the kernel alone is
+    timed through lqk_detector, and the difference is the decision pass's share.  8 m n flops per sample
+    against the 157.3 TFLOP/s float32 vector peak.  Beside each shape the same rows composed from what the
+    library had before the object: m firfilt_cccf with the reversed templates, autocorr_cccf's e2 for the
+    energy, and a torch normalise and row maximum.  Every side is timed three times in turn with the same
+    counts (3 warm-up calls, 10 timed); "ms" is the median, "runs_ms" all three."""
+    import ctypes as C
+
+    import numpy as np
+    n = 1 << 24
+    peak = 157.3e12
+    x = cbuf(n)
+    xc = torch.view_as_complex(x.view(-1, 2))
+    rng = np.random.default_rng(3)
+    for ln, m in ((64, 2), (256, 4), (1341, 11), (512, 16)):
+        s = (rng.integers(0, 2, ln) * 2.0 - 1.0).astype(np.complex64)
+        dphi_max = 0.0 if m == 2 else (m - 0.5) * 0.8 * np.pi / ln
+        q = LQ.Detector(s, 0.6, dphi_max)
+        assert q.device_eligible and q.num_correlators == m
+        q.set_stream(S)
+        drxy = torch.empty(n * m, device="cuda")
+        cnt = [0]
+
+        def call(rows):
+            cnt[0] = q.correlate_block_dev(x.data_ptr(), n, drxy.data_ptr() if rows else 0, max_det=4)[0]
+        # the kernel alone
+        P = q.templates()
+        pad = (ln + 3) & ~3
+        pt = np.zeros((pad, m), np.complex64)
+        pt[:ln] = P.T
+        dpt = torch.view_as_real(torch.from_numpy(pt).cuda()).contiguous()
+        hist = torch.zeros(2 * 2 * ln, device="cuda")
+        cap = 1 << 17
+        nt = (n + LQ.Detector.TILE - 1) // LQ.Detector.TILE
+        lst = torch.zeros(4 + nt + cap * (2 + m), dtype=torch.int32, device="cuda")
+        edge = torch.zeros(2 * nt * (2 + m), dtype=torch.int32, device="cuda")
+        fn = L.lqk_detector
+        fn.restype = None
+        fn.argtypes = [C.c_uint, C.c_uint, C.c_float] + [C.c_void_p] * 3 + [C.c_ulonglong, C.c_void_p, C.c_void_p,
+                                                                           C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p]
+
+        def kernel(rows):
+            fn(ln, m, 0.6, dpt.data_ptr(), hist.data_ptr(), x.data_ptr(), n, drxy.data_ptr() if rows else None,
+               lst.data_ptr(), cap, edge.data_ptr(), hist.data_ptr() + 8 * ln, S)
+        # the composition: m firfilt_cccf + autocorr e2 + torch
+        filts = []
+        for k in range(m):
+            f = LQ.FirFilt("cccf", np.ascontiguousarray(P[k][::-1]))
+            f.set_stream(S)
+            filts.append(f)
+        ac = LQ.AutoCorr("cccf", ln, 0)
+        ac.set_stream(S)
+        y = torch.empty(m, 2 * n, device="cuda")
+        rxx = torch.empty(2 * n, device="cuda")
+        e2 = torch.empty(n, device="cuda")
+        rmax = torch.empty(n, device="cuda")
+        yc = torch.view_as_complex(y.view(m, n, 2))
+
+        def composed():
+            for k, f in enumerate(filts):
+                f.execute_block_dev(x.data_ptr(), n, y[k].data_ptr())
+            ac.execute_block_dev(x.data_ptr(), n, rxx.data_ptr(), e2.data_ptr())
+            with torch.cuda.stream(STREAM):
+                r = yc.abs() / torch.sqrt(e2 * float(ln))[None, :]
+                torch.amax(r, dim=0, out=rmax)
+        # three rounds over all five, the same warm-up and iteration counts for each; the median counts
+        sides = (("call", lambda: call(False)), ("call + drxy", lambda: call(True)), ("kernel", lambda: kernel(False)),
+                 ("kernel + drxy", lambda: kernel(True)), ("composed", composed))
+        runs = {k: [] for k, _ in sides}
+        for _ in range(3):
+            for k, f in sides:
+                runs[k].append(timed(f, it=10, w=3))
+        med = {k: sorted(v)[1] for k, v in runs.items()}
+        for k, _ in sides:
+            row = {"workload": "detector_cccf n=%d m=%d, %s" % (ln, m, k), "ms": round(med[k], 4),
+                   "runs_ms": [round(v, 4) for v in runs[k]]}
+            if k != "composed":
+                row["frac_of_fp32_vector_peak"] = round(8.0 * m * ln * n / (med[k] * 1e-3) / peak, 3)
+            if k.startswith("call"):
+                row["decision_pass_share_of_call"] = round(max(1.0 - med[k.replace("call", "kernel")] / med[k], 0.0), 4)
+                row["over_composed"] = round(med[k] / med["composed"], 4)
+                row["detections"] = cnt[0]
+            print(json.dumps(row))
+        sys.stdout.flush()
+        q.destroy()
+        for f in filts:
+            f.destroy()
+        ac.destroy()
+        del y, yc, drxy, rxx, e2, rmax
+
+
 def main():
     L = LQ.lib()
+    if "--detector" in sys.argv[1:]:
+        detector_rows(L)
+        return
     if "--autocorr" in sys.argv[1:]:
         autocorr_rows(L)
         return
