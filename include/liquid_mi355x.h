@@ -755,6 +755,110 @@ unsigned int liquid_mi355x_detector_max_correlators(void);
 void liquid_mi355x_detector_set_list_capacity(unsigned int _records);
 
 /* ------------------------------------------------------------------------ */
+/* qdetector_cccf (liquid.h "qdetector_cccf"): FFT preamble detector         */
+/* ------------------------------------------------------------------------ */
+/* The stream is cut into windows of nfft = 2^nextpow2(2 s_len) samples that
+   overlap by half.  Each window is transformed, multiplied by conj(S) (S =
+   FFT(s zero padded)) shifted by every carrier offset in [-range, range],
+   transformed back, and the largest |rxy| over all offsets and lags, scaled by
+   g = 1 / (nfft sqrt(energy) sqrt(s_len / nfft) sqrt(sum |s|^2)), is the
+   window's peak (qdetector_cccf.c:373-477).  A window with peak > threshold
+   && index < nfft - s_len starts the align stage: the buffer is realigned to
+   the peak, filled, and tau_hat, gamma_hat, dphi_hat, phi_hat are estimated
+   (:480-607).  execute() returns the object's nfft aligned samples (host
+   memory) at the sample that completes them, NULL at every other sample.
+   create_linear keeps the reference's argument checks; set_threshold (0, 2]
+   and set_range [0, 0.5] ignore values out of range with a warning.
+   qdetector_cccf_create_gmsk is not provided (there is no gmskmod).
+
+   What is held to, and where this differs from the reference:
+   1. A seek window's record depends only on that window's nfft samples.
+      energy = x2_sum_0 + x2_sum_1, each a fixed-order float32 sum over its
+      own half window (the reference keeps a running sum in arrival order).
+   2. The object carries the buffered samples, the counter, the state, the
+      coarse offset and the estimates between calls, and every window goes
+      through the same device code: records and detections of block calls are
+      bit identical however the stream is cut into calls, across host and
+      device pointers and alignments of the input.
+   3. execute() buffers on the host and sends a window through that same
+      device path when it fills, once per nfft/2 samples; per-sample and block
+      calls may be mixed and agree bit for bit.
+   4. Where energy == 0 the record is (0, 0, 0) and nothing is detected (the
+      reference forms 0 inf = NaN, which compares above nothing).
+   5. The peak is the first maximum in the reference's order: offset ascending
+      from -range, then lag ascending; squared magnitudes are compared.
+   6. A seek hit at index == 0: the window is already aligned and the align
+      stage runs on it at once (the reference sets counter = nfft and writes
+      one element past its buffer at the next sample).
+   7. reset() returns the object to its state after create and keeps
+      threshold and range (it is empty in the reference).
+   8. After a frame seek resumes as in the reference: the window grid restarts
+      at (frame start + nfft/2).
+
+   Extensions.  execute_block reports every frame completed within _x[0.._n):
+   it returns their number and writes the first _max_det of them: _idx (index
+   within this call of the sample at which execute() would have returned
+   non-NULL), the four estimates, and in _frames (NULL, or _max_det x nfft
+   samples) the aligned buffers.  _records (NULL, or room for
+   1 + (_n + nfft) / (nfft / 2) records) receives one record per seek window
+   completed in the call, in stream order, *_num_records their number.
+   execute_block_dev takes _dx in device memory; _frames and _records are then
+   device pointers (or NULL) and stay on the device; only each chunk's records
+   and, per detection, the scalars cross the bus, so the call synchronises the
+   object's stream.  Any output pointer may be NULL. */
+typedef struct {
+    float peak;          /* g max |rxy| */
+    unsigned int index;  /* its lag */
+    int offset;          /* its carrier offset (bins) */
+    float energy;        /* sum |x|^2 of the window */
+} qdetector_cccf_record;
+typedef struct qdetector_cccf_s *qdetector_cccf;
+qdetector_cccf qdetector_cccf_create(liquid_float_complex *_s, unsigned int _s_len);
+qdetector_cccf qdetector_cccf_create_linear(liquid_float_complex *_sequence, unsigned int _sequence_len, int _ftype,
+                                            unsigned int _k, unsigned int _m, float _beta);
+void qdetector_cccf_destroy(qdetector_cccf _q);
+void qdetector_cccf_print(qdetector_cccf _q);
+void qdetector_cccf_reset(qdetector_cccf _q);
+void *qdetector_cccf_execute(qdetector_cccf _q, liquid_float_complex _x);
+void qdetector_cccf_set_threshold(qdetector_cccf _q, float _threshold);
+void qdetector_cccf_set_range(qdetector_cccf _q, float _dphi_max);
+unsigned int qdetector_cccf_get_seq_len(qdetector_cccf _q);
+const void *qdetector_cccf_get_sequence(qdetector_cccf _q);
+unsigned int qdetector_cccf_get_buf_len(qdetector_cccf _q);
+float qdetector_cccf_get_tau(qdetector_cccf _q);
+float qdetector_cccf_get_gamma(qdetector_cccf _q);
+float qdetector_cccf_get_dphi(qdetector_cccf _q);
+float qdetector_cccf_get_phi(qdetector_cccf _q);
+unsigned int qdetector_cccf_execute_block(qdetector_cccf _q, const liquid_float_complex *_x, unsigned long long _n,
+                                          unsigned int _max_det, unsigned long long *_idx, float *_tau_hat,
+                                          float *_gamma_hat, float *_dphi_hat, float *_phi_hat,
+                                          liquid_float_complex *_frames, qdetector_cccf_record *_records,
+                                          unsigned long long *_num_records);
+unsigned int qdetector_cccf_execute_block_dev(qdetector_cccf _q, const liquid_float_complex *_dx,
+                                              unsigned long long _n, unsigned int _max_det, unsigned long long *_idx,
+                                              float *_tau_hat, float *_gamma_hat, float *_dphi_hat, float *_phi_hat,
+                                              liquid_float_complex *_dframes, qdetector_cccf_record *_drecords,
+                                              unsigned long long *_num_records);
+int qdetector_cccf_get_range(qdetector_cccf _q);        /* in bins */
+float qdetector_cccf_get_threshold(qdetector_cccf _q);
+void qdetector_cccf_set_stream(qdetector_cccf _q, void *_hip_stream);
+void qdetector_cccf_synchronize(qdetector_cccf _q);
+/* the seek kernel a launch takes (fused at nfft 512 and 1024, composed
+   elsewhere) -- a function of nfft alone, so that a window's bits do not
+   depend on how many windows a call completes */
+enum { LIQUID_MI355X_QDETECTOR_COMPOSED = 0, LIQUID_MI355X_QDETECTOR_FUSED = 1 };
+int liquid_mi355x_qdetector_route(unsigned int _nfft, int _range, unsigned long long _num_windows);
+/* tests only: seek windows per launch chunk (0: the default, which depends on
+   nfft alone); results do not depend on it.  Measurements only: set_route
+   (LIQUID_MI355X_QDETECTOR_COMPOSED) sends every size's later launches to the
+   composed path, and liquid_mi355x_qdetector_route answers accordingly; -1
+   restores the default.  Both settings are process-wide and not thread-safe:
+   set them while no other thread runs a qdetector. */
+void liquid_mi355x_qdetector_set_route(int _route);
+void liquid_mi355x_qdetector_set_chunk(unsigned int _windows);
+unsigned int liquid_mi355x_qdetector_chunk(unsigned int _nfft);
+
+/* ------------------------------------------------------------------------ */
 /* fftfilt (liquid.h:2192-2240): rrrf, crcf, cccf                            */
 /* ------------------------------------------------------------------------ */
 #define LQMI_FFTFILT_API(FFTFILT, TO, TC, TI)                                                   \

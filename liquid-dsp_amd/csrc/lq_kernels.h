@@ -552,6 +552,39 @@ void lqk_detector(unsigned int len, unsigned int m, float thr, const void *pt, c
                   unsigned long long n, float *drxy, unsigned int *list, unsigned int cap, unsigned int *edge,
                   void *hist_new, void *stream);
 
+/* ---------------------------------------------------------------- qdetector (k_qdetector.hip)
+ * The stream a call sees is ext = carry (clen samples) ++ x.  seek: the records
+ * (4 words each: peak, index, offset, energy; rec 16-byte aligned device or
+ * pinned host memory) of the nw windows ext[pos + w nfft/2 .. + nfft), each a
+ * function of its own nfft samples, S (FFT of the zero-padded template), range,
+ * s_len and s2_sum alone.  nfft a power of two >= 2, 2 range + 1 <= nfft.
+ * route: lqk_qdetector_route(nfft) -- FUSED (nfft = 512: 32 lanes per window,
+ * nfft = 1024: one wave), nothing but the record leaves the CU, scratch unused
+ * (a FUSED launch of any other nfft is refused); COMPOSED (any nfft):
+ * gather, lqk_fft_any, shifted products for nb offsets at a time (at most
+ * LQK_QD_PRODUCT_SAMPLES values, at least one offset), lqk_fft_any back, fold;
+ * scratch: lqk_qdetector_scratch_bytes(nfft, range, nw, &nb) bytes. */
+enum { LQK_QD_ROUTE_COMPOSED = 0, LQK_QD_ROUTE_FUSED = 1 };
+#define LQK_QD_PRODUCT_SAMPLES (1ull << 23)
+int lqk_qdetector_route(unsigned int nfft);
+size_t lqk_qdetector_scratch_bytes(unsigned int nfft, int range, unsigned long long nw, unsigned int *nb);
+void lqk_qdetector_seek(int route, unsigned int nfft, unsigned int s_len, float s2_sum, int range, const void *S,
+                        const void *carry, unsigned long long clen, const void *x, unsigned long long pos,
+                        unsigned long long nw, void *scratch, void *rec, void *stream);
+/* S = FFT(s_padded) (nfft values each); work: lqk_fft_work_bytes(nfft, 1) */
+void lqk_qdetector_spectrum(unsigned int nfft, const void *s_padded, void *S, void *work, void *stream);
+/* align stage over the frame ext[pos .. pos + nfft): frame receives it; out13 =
+ * (re, im) of IFFT(X conj(S shifted by offset)) at lags -1, 0, +1, the first
+ * arg-max bin i0 of FFT(frame conj(s) zero padded), (re, im) of its bins i0 - 1,
+ * i0, i0 + 1.  scratch: lqk_qdetector_align_bytes(nfft); its first nfft values
+ * are left holding frame conj(s), which lqk_qdetector_metric sums as
+ * sum_{i < s_len} . exp(-j dphi i) into out2 (fixed order) */
+size_t lqk_qdetector_align_bytes(unsigned int nfft);
+void lqk_qdetector_align(unsigned int nfft, unsigned int s_len, int offset, const void *S, const void *s,
+                         const void *carry, unsigned long long clen, const void *x, unsigned long long pos,
+                         void *frame, void *scratch, void *out13, void *stream);
+void lqk_qdetector_metric(unsigned int s_len, float dphi, const void *scratch, void *out2, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

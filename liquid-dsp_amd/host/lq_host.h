@@ -395,6 +395,58 @@ unsigned long long nco_plan_reduce(const nco_plan *pl, unsigned long long g);
 /* the phase at position g: the checkpoint before it stepped forward */
 float nco_plan_at(const nco_plan *pl, unsigned long long g);
 
+/* ---- qdetector's walk (host/qdetector_walk.c): the decisions over window
+ * records, the realignment arithmetic and the closed-form estimates -- no
+ * runtime call, no kernel launch, libc and libm alone.
+ *
+ * A call sees the stream ext = (the `counter` samples carried from earlier
+ * calls) ++ (its n new samples), `total` long.  `base` is the ext position of
+ * the seek grid's origin (SEEK: windows start at base + w nfft/2) or of the
+ * frame being aligned (ALIGN).  qdw_next names the next piece of device work;
+ * qdw_seek takes the records of windows base, base + nfft/2, ... in order and
+ * stops at the first detection; qdw_align_fit / qdw_align_finish take the
+ * align stage's scalars and restart the grid half a buffer into the frame;
+ * qdw_end leaves ext[base .. total) as the next call's carried samples. */
+enum { QDW_SEEK = 0, QDW_ALIGN = 1 };
+enum { QDW_DO_SEEK = 0, QDW_DO_ALIGN = 1, QDW_DO_END = 2 };
+typedef struct {
+    unsigned int nfft, s_len;
+    float s2_sum, threshold;
+    int range;
+    /* carried between calls */
+    int state;
+    unsigned int counter;             /* samples held: SEEK [nfft/2, nfft), ALIGN (s_len, nfft) */
+    int offset;                       /* coarse carrier offset of the frame being aligned */
+    float tau_hat, gamma_hat, dphi_hat, phi_hat;
+    /* within a call */
+    unsigned long long total, base, c0;
+} qd_walk;
+
+void qdw_init(qd_walk *w, unsigned int nfft, unsigned int s_len, float s2_sum);
+void qdw_reset(qd_walk *w);           /* the state after create; threshold and range stay */
+int qdw_set_threshold(qd_walk *w, float threshold);   /* 0: out of range, ignored */
+int qdw_set_range(qd_walk *w, float dphi_max);
+void qdw_begin(qd_walk *w, unsigned long long n);
+/* DO_SEEK: *count whole windows from ext position *pos; DO_ALIGN: the frame's
+ * nfft samples start at *pos; DO_END: *count samples from *pos are carried */
+int qdw_next(const qd_walk *w, unsigned long long *pos, unsigned long long *count);
+/* records of the nrec windows from base; returns how many of them the seek
+ * stage completed (the detecting one is the last) */
+unsigned long long qdw_seek(qd_walk *w, const qdetector_cccf_record *rec, unsigned long long nrec);
+int qdw_detects(const qd_walk *w, const qdetector_cccf_record *rec);
+/* rxy: (re, im) of the lags -1, 0, +1 at the coarse offset, unscaled; i0: the
+ * arg-max bin of FFT(x conj s); v: (re, im) of the bins i0 - 1, i0, i0 + 1 */
+void qdw_align_fit(qd_walk *w, const float rxy[6], unsigned int i0, const float v[6]);
+/* metric: the de-rotation sum; returns the index within this call of the
+ * sample that completed the frame.  After qdw_begin(w, 0) on a full buffer
+ * (execute(): the completing sample arrived before the call) there is no such
+ * sample and ~0ull is returned */
+unsigned long long qdw_align_finish(qd_walk *w, float mre, float mim);
+void qdw_end(qd_walk *w);
+/* the closed forms (qdetector_cccf.c:504-514, 553-562) */
+void qdw_fit_tau_gamma(float aneg, float a0, float apos, unsigned int nfft, float s2_sum, float *tau, float *gamma);
+float qdw_fit_dphi(unsigned int i0, float vneg, float v0, float vpos, unsigned int nfft);
+
 /* generic dotprod engine */
 typedef struct lq_dotprod_s lq_dotprod;
 lq_dotprod *lq_dotprod_create(int kind, const float *h, unsigned int n);

@@ -518,6 +518,31 @@ def _declare(L):
         "liquid_mi355x_detector_max_len": (u, []),
         "liquid_mi355x_detector_max_correlators": (u, []),
         "liquid_mi355x_detector_set_list_capacity": (None, [u]),
+        "qdetector_cccf_create": (vp, [vp, u]),
+        "qdetector_cccf_create_linear": (vp, [vp, u, i, u, u, f]),
+        "qdetector_cccf_destroy": (None, [vp]),
+        "qdetector_cccf_print": (None, [vp]),
+        "qdetector_cccf_reset": (None, [vp]),
+        "qdetector_cccf_execute": (vp, [vp, cfloat]),
+        "qdetector_cccf_set_threshold": (None, [vp, f]),
+        "qdetector_cccf_set_range": (None, [vp, f]),
+        "qdetector_cccf_get_seq_len": (u, [vp]),
+        "qdetector_cccf_get_sequence": (vp, [vp]),
+        "qdetector_cccf_get_buf_len": (u, [vp]),
+        "qdetector_cccf_get_tau": (f, [vp]),
+        "qdetector_cccf_get_gamma": (f, [vp]),
+        "qdetector_cccf_get_dphi": (f, [vp]),
+        "qdetector_cccf_get_phi": (f, [vp]),
+        "qdetector_cccf_execute_block": (u, [vp, vp, ull, u, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "qdetector_cccf_execute_block_dev": (u, [vp, vp, ull, u, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "qdetector_cccf_get_range": (i, [vp]),
+        "qdetector_cccf_get_threshold": (f, [vp]),
+        "qdetector_cccf_set_stream": (None, [vp, vp]),
+        "qdetector_cccf_synchronize": (None, [vp]),
+        "liquid_mi355x_qdetector_route": (i, [u, i, ull]),
+        "liquid_mi355x_qdetector_set_chunk": (None, [u]),
+        "liquid_mi355x_qdetector_set_route": (None, [i]),
+        "liquid_mi355x_qdetector_chunk": (u, [u]),
     })
     sig.update({
         "nco_crcf_create": (vp, [i]),
@@ -1486,6 +1511,114 @@ class Detector(_Obj):
                                                    ptr(est[2]), max_det))
         k = min(cnt, max_det)
         return cnt, idx[:k], est[0][:k], est[1][:k], est[2][:k]
+
+
+QDETECTOR_ROUTES = ("composed", "fused")
+QDETECTOR_RECORD = np.dtype([("peak", np.float32), ("index", np.uint32), ("offset", np.int32),
+                             ("energy", np.float32)])
+
+
+def qdetector_route(nfft, rng=0, num_windows=1):
+    """The seek kernel a qdetector launch takes (liquid_mi355x_qdetector_route)."""
+    return QDETECTOR_ROUTES[lib().liquid_mi355x_qdetector_route(int(nfft), int(rng), int(num_windows))]
+
+
+def set_qdetector_chunk(windows):
+    """Seek windows per launch chunk of the qdetector (0: the default).  For tests."""
+    lib().liquid_mi355x_qdetector_set_chunk(int(windows))
+
+
+def set_qdetector_route(route):
+    """"composed": every size's later launches take the composed path (and
+    qdetector_route says so); None: the default.  For measurements."""
+    lib().liquid_mi355x_qdetector_set_route(-1 if route is None else QDETECTOR_ROUTES.index(route))
+
+
+def qdetector_chunk(nfft):
+    return int(lib().liquid_mi355x_qdetector_chunk(int(nfft)))
+
+
+class QDetector(_Obj):
+    """qdetector_cccf: FFT preamble detector with a carrier sweep.  s: the
+    template samples, or with linear=(ftype, k, m, beta) the symbols of
+    create_linear.  execute(v) returns None or the nfft aligned samples;
+    the block calls return a dict: count, idx, tau, gamma, dphi, phi (arrays
+    of min(count, max_det)), frames (host call with frames=True), records
+    (host call: a QDETECTOR_RECORD array) and num_records."""
+    prefix = "qdetector_cccf"
+
+    def __init__(self, s, linear=None):
+        s = _samples(s, CCCF)
+        if linear is None:
+            self.q = self._fn("_create")(ptr(s), len(s))
+        else:
+            ftype, k, m, beta = linear
+            code = LIQUID_FIRFILT[ftype] if isinstance(ftype, str) else int(ftype)
+            self.q = self._fn("_create_linear")(ptr(s), len(s), code, k, m, float(beta))
+        self.nfft = int(self._fn("_get_buf_len")(self.q))
+        self.s_len = int(self._fn("_get_seq_len")(self.q))
+
+    def sequence(self):
+        p = self._fn("_get_sequence")(self.q)
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), (2 * self.s_len,)).view(np.complex64).copy()
+
+    def reset(self):
+        self._fn("_reset")(self.q)
+
+    def synchronize(self):
+        self._fn("_synchronize")(self.q)
+
+    def set_threshold(self, v):
+        self._fn("_set_threshold")(self.q, float(v))
+
+    def set_range(self, v):
+        self._fn("_set_range")(self.q, float(v))
+
+    @property
+    def threshold(self):
+        return float(self._fn("_get_threshold")(self.q))
+
+    @property
+    def range(self):
+        return int(self._fn("_get_range")(self.q))
+
+    def estimates(self):
+        """(tau_hat, gamma_hat, dphi_hat, phi_hat) of the last frame, float32"""
+        return tuple(np.float32(self._fn(n)(self.q)) for n in ("_get_tau", "_get_gamma", "_get_dphi", "_get_phi"))
+
+    def execute(self, v):
+        p = self._fn("_execute")(self.q, _by_value(v, CCCF))
+        if not p:
+            return None
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_float)), (2 * self.nfft,)).view(np.complex64).copy()
+
+    def _call(self, name, x, n, max_det, frames, records):
+        idx = np.full(max_det, np.iinfo(np.uint64).max, np.uint64)
+        est = [np.full(max_det, np.float32(-77.0)) for _ in range(4)]
+        nrec = C.c_ulonglong(0)
+        cnt = int(self._fn(name)(self.q, x, n, max_det, ptr(idx), ptr(est[0]), ptr(est[1]), ptr(est[2]), ptr(est[3]),
+                                 frames, records, C.cast(C.byref(nrec), C.c_void_p)))
+        k = min(cnt, max_det)
+        return {"count": cnt, "idx": idx[:k], "tau": est[0][:k], "gamma": est[1][:k], "dphi": est[2][:k],
+                "phi": est[3][:k], "num_records": int(nrec.value)}
+
+    def execute_block(self, x, max_det=16, frames=False, records=True):
+        """host pointers"""
+        x = _samples(x, CCCF)
+        fr = np.zeros((max_det, self.nfft), np.complex64) if frames else None
+        rec = np.zeros(1 + (len(x) + self.nfft) // (self.nfft // 2), QDETECTOR_RECORD) if records else None
+        r = self._call("_execute_block", ptr(x), len(x), max_det, None if fr is None else ptr(fr),
+                       None if rec is None else ptr(rec))
+        if fr is not None:
+            r["frames"] = fr[:len(r["idx"])]
+        if rec is not None:
+            r["records"] = rec[:r["num_records"]]
+        return r
+
+    def execute_block_dev(self, dx, n, max_det=16, dframes=0, drecords=0):
+        """dx: n samples in device memory; dframes / drecords: 0 or device
+        memory.  Waits for the object's stream."""
+        return self._call("_execute_block_dev", dx, n, max_det, dframes or None, drecords or None)
 
 
 LIQUID_NCO, LIQUID_VCO = 0, 1

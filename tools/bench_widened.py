@@ -9,6 +9,7 @@ GB/s (bytes stated per workload) as a fraction of the 8 TB/s spec.
     python tools/bench_widened.py --iir           (the iirfilt, iirdecim and iirinterp rows alone)
     python tools/bench_widened.py --autocorr      (the autocorr rows alone)
     python tools/bench_widened.py --detector      (the detector_cccf rows alone)
+    python tools/bench_widened.py --qdetector     (the qdetector_cccf rows alone)
 """
 import json
 import os
@@ -335,8 +336,93 @@ def detector_rows(L):
         del y, yc, drxy, rxx, e2, rmax
 
 
+def qdetector_rows(L):
+    """qdetector_cccf, 2^24 samples of noise in device memory (no window detects), (s_len, range) = (156, 24),
+    (284, 48), (540, 97), (2710, 391): nfft 512, 1024, 2048, 8192.  A call returns after its last chunk's records
+    are on the host (events around synchronous calls).  Beside each shape what a user could do without the
+    object: windows gathered with torch (unfold), fft_execute_batch_dev forward, torch for the shifted
+    products, fft_execute_batch_dev backward, torch for abs and max, in pieces of 2^25 values
+    ("plan API + torch"); and at the sizes with a fused kernel the library's own composed path
+    (liquid_mi355x_qdetector_set_route) beside it.  Flops: (1 + offsets) transforms of 5 nfft log2 nfft and
+    9 nfft per offset for the product and the magnitude, per window, against the 157.3 TFLOP/s float32 vector
+    peak.  Every side is timed three times in turn (1 warm-up call, 3 timed); "ms" is the median."""
+    import numpy as np
+    n = 1 << 24
+    peak = 157.3e12
+    x = cbuf(n)
+    xc = torch.view_as_complex(x.view(-1, 2))
+    rng = np.random.default_rng(5)
+    for s_len, r in ((156, 24), (284, 48), (540, 97), (2710, 391)):
+        s = ((rng.integers(0, 2, s_len) * 2.0 - 1.0) + 1j * (rng.integers(0, 2, s_len) * 2.0 - 1.0)).astype(np.complex64)
+        q = LQ.QDetector(s)
+        nfft = q.nfft
+        q.set_range((r + 0.5) * 2 * np.pi / nfft)
+        assert q.range == r
+        q.set_stream(S)
+        route = LQ.qdetector_route(nfft)
+        noff, h = 2 * r + 1, nfft // 2
+        nwin = (n - nfft) // h + 1
+        Sf = torch.fft.fft(torch.cat([torch.from_numpy(s).cuda(), torch.zeros(nfft - s_len, dtype=torch.complex64, device="cuda")]))
+        idx = (torch.arange(nfft, device="cuda")[None, :] - torch.arange(-r, r + 1, device="cuda")[:, None]) % nfft
+        Sc = torch.conj(Sf)[idx]                              # noff x nfft
+        piece = max(1, (1 << 25) // (noff * nfft))
+        fwd, bwd = L.fft_create_plan(nfft, None, None, +1, 0), L.fft_create_plan(nfft, None, None, -1, 0)
+        L.fft_set_stream(fwd, S)
+        L.fft_set_stream(bwd, S)
+        W = torch.empty(piece, nfft, dtype=torch.complex64, device="cuda")
+        X = torch.empty_like(W)
+        P = torch.empty(piece, noff, nfft, dtype=torch.complex64, device="cuda")
+        R = torch.empty_like(P)
+        cnt = [0]
+
+        def call(composed):
+            LQ.set_qdetector_route("composed" if composed else None)
+            try:
+                cnt[0] = q.execute_block_dev(x.data_ptr(), n, max_det=4)["count"]
+            finally:
+                LQ.set_qdetector_route(None)
+
+        def by_plan_api():
+            with torch.cuda.stream(STREAM):
+                win = xc.unfold(0, nfft, h)
+                best = []
+                for w0 in range(0, win.shape[0], piece):
+                    k = min(piece, win.shape[0] - w0)
+                    W[:k].copy_(win[w0:w0 + k])
+                    L.fft_execute_batch_dev(fwd, W.data_ptr(), X.data_ptr(), k)
+                    torch.mul(X[:k, None, :], Sc[None], out=P[:k])
+                    L.fft_execute_batch_dev(bwd, P.data_ptr(), R.data_ptr(), k * noff)
+                    best.append(torch.max(R[:k].abs().reshape(k, -1), dim=1))
+                return best
+        sides = [("call", lambda: call(False)), ("plan API + torch", by_plan_api)]
+        if route != "composed":
+            sides.insert(1, ("call, composed path", lambda: call(True)))
+        runs = {k: [] for k, _ in sides}
+        for _ in range(3):
+            for k, f in sides:
+                runs[k].append(timed(f, it=3, w=1, floor_ms=0.0))
+        med = {k: sorted(v)[1] for k, v in runs.items()}
+        flops = nwin * ((1 + noff) * 5.0 * nfft * np.log2(nfft) + noff * 9.0 * nfft)
+        for k, _ in sides:
+            row = {"workload": "qdetector_cccf s_len=%d range=%d nfft=%d (%s), %s" % (s_len, r, nfft, route, k),
+                   "ms": round(med[k], 3), "runs_ms": [round(v, 3) for v in runs[k]]}
+            if k != "plan API + torch":
+                row["frac_of_fp32_vector_peak"] = round(flops / (med[k] * 1e-3) / peak, 4)
+                row["over_plan_api"] = round(med[k] / med["plan API + torch"], 4)
+                row["detections"] = cnt[0]
+            print(json.dumps(row))
+        sys.stdout.flush()
+        q.destroy()
+        L.fft_destroy_plan(fwd)
+        L.fft_destroy_plan(bwd)
+        del Sc, idx, W, X, P, R
+
+
 def main():
     L = LQ.lib()
+    if "--qdetector" in sys.argv[1:]:
+        qdetector_rows(L)
+        return
     if "--detector" in sys.argv[1:]:
         detector_rows(L)
         return
