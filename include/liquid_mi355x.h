@@ -1071,6 +1071,29 @@ int liquid_mi355x_get_small_calls(void);
  * workgroup.  0 (default): no limit.  Results do not depend on it. */
 void liquid_mi355x_set_max_workgroups(unsigned int _n);
 unsigned int liquid_mi355x_get_max_workgroups(void);
+/* The two staging seams of a host-pointer call (no reference counterpart; for
+ * tests): an input of up to _pinned_input_max bytes is copied to pinned host
+ * memory that the kernel reads in place, a larger one goes to device memory
+ * by DMA; a result of up to _copyout_max bytes returns through the copy-out
+ * kernel and its completion flag, a larger one by DMA and a stream sync. */
+unsigned int liquid_mi355x_pinned_input_max(void);
+unsigned int liquid_mi355x_copyout_max(void);
+/* Which launch a dotprod batch call of _nvec rows of _n samples takes (_kind:
+ * 0 rrrf, 1 crcf, 2 cccf; _x_aligned16: the input pointer is 16-byte aligned),
+ * computed by the launch's own decision (no GPU call).  Bit 4
+ * (LIQUID_MI355X_DOTPROD_VEC): k_dot_vec, 16-byte loads -- _n a multiple of
+ * the chunk (4 real, 2 complex samples) and an aligned input; clear:
+ * k_dot_scalar.  Bits 0-3 (LIQUID_MI355X_DOTPROD_LG_MASK): lg G, G = 1, 2, 4,
+ * 8 or 16 lanes per row.  -1: invalid kind.  _blocks: the grid of that launch,
+ * 256 lanes each, at most _block_cap; a capped grid walks the rows in
+ * ceil(_nvec G / (256 _blocks)) passes. */
+enum {
+    LIQUID_MI355X_DOTPROD_LG_MASK = 15,
+    LIQUID_MI355X_DOTPROD_VEC = 16
+};
+int liquid_mi355x_dotprod_route(int _kind, unsigned int _n, int _x_aligned16, unsigned long long _nvec);
+unsigned int liquid_mi355x_dotprod_blocks(int _kind, unsigned int _n, int _x_aligned16, unsigned long long _nvec);
+unsigned int liquid_mi355x_dotprod_block_cap(void);
 /* Which kernel a firdecim device call of _nout outputs takes (_kind: 0 rrrf,
  * 1 crcf, 2 cccf; _x_aligned16: the input pointer is 16-byte aligned), and
  * the outputs per tile and the grid cap of that launch (0: not capped). */

@@ -140,39 +140,68 @@ __global__ __launch_bounds__(NT) void k_dot_scalar(const float *__restrict__ h, 
     }
 }
 
-template <int KIND>
-void launch(const void *h, unsigned n, const void *X, long long stride, long long nvec, void *Y, hipStream_t st)
+constexpr long long GRID_CAP = 256 * 16; // grid-stride beyond 16 blocks per CU
+
+// the launch's decision: the kernel, the lanes per vector and the grid
+struct dot_route {
+    bool vec;
+    int G, lg;
+    long long blocks;
+};
+
+// aligned16: X and h are both 16-byte aligned
+dot_route dotprod_route(int kind, unsigned n, long long stride, bool aligned16, long long nvec)
 {
-    const int VEC = dp<KIND>::VEC;
-    const size_t esz = KIND == 0 ? 4 : 8;
-    const bool vec_ok = (n % VEC == 0) && ((stride * esz) % 16 == 0) && (((uintptr_t)X & 15) == 0) &&
-                        (((uintptr_t)h & 15) == 0);
-    const long long work = vec_ok ? n / VEC : n; // elements a group walks
+    const int VEC = kind == 0 ? dp<0>::VEC : dp<1>::VEC;
+    const size_t esz = kind == 0 ? 4 : 8;
+    dot_route r;
+    r.vec = (n % VEC == 0) && ((stride * esz) % 16 == 0) && aligned16;
+    const long long work = r.vec ? n / VEC : n; // elements a group walks
     // at most 8 (n <= 128 complex) or 16 lanes per vector: each lane keeps
     // several 16-byte loads in flight and the shuffle reduction stays short
     // (dotprod_cccf 2^20 vectors: n=64 0.61-0.69 -> 0.82, n=256 0.76 -> 0.83
     // of the 8 TB/s spec; 64 lanes per vector before)
     const int gmax = work <= 64 ? 8 : 16;
-    int G = 1, lg = 0;
-    while (G < gmax && (long long)G * 2 <= work) {
-        G <<= 1;
-        lg++;
+    r.G = 1;
+    r.lg = 0;
+    while (r.G < gmax && (long long)r.G * 2 <= work) {
+        r.G <<= 1;
+        r.lg++;
     }
     long long groups = nvec;
-    long long threads = groups * G;
-    long long blocks = (threads + NT - 1) / NT;
-    if (blocks > 256 * 16) blocks = 256 * 16; // grid-stride beyond 16 blocks per CU
-    if (blocks < 1) blocks = 1;
-    if (vec_ok)
-        hipLaunchKernelGGL(k_dot_vec<KIND>, dim3((unsigned)blocks), dim3(NT), 0, st, (const float *)h, (int)n,
-                           (const float *)X, stride * (long long)(esz / 4), nvec, (float *)Y, G, lg);
+    long long threads = groups * r.G;
+    r.blocks = (threads + NT - 1) / NT;
+    if (r.blocks > GRID_CAP) r.blocks = GRID_CAP;
+    if (r.blocks < 1) r.blocks = 1;
+    return r;
+}
+
+template <int KIND>
+void launch(const void *h, unsigned n, const void *X, long long stride, long long nvec, void *Y, hipStream_t st)
+{
+    const size_t esz = KIND == 0 ? 4 : 8;
+    const dot_route r =
+        dotprod_route(KIND, n, stride, (((uintptr_t)X & 15) == 0) && (((uintptr_t)h & 15) == 0), nvec);
+    if (r.vec)
+        hipLaunchKernelGGL(k_dot_vec<KIND>, dim3((unsigned)r.blocks), dim3(NT), 0, st, (const float *)h, (int)n,
+                           (const float *)X, stride * (long long)(esz / 4), nvec, (float *)Y, r.G, r.lg);
     else
-        hipLaunchKernelGGL(k_dot_scalar<KIND>, dim3((unsigned)blocks), dim3(NT), 0, st, (const float *)h, (int)n,
-                           (const float *)X, stride, nvec, (float *)Y, G, lg);
+        hipLaunchKernelGGL(k_dot_scalar<KIND>, dim3((unsigned)r.blocks), dim3(NT), 0, st, (const float *)h, (int)n,
+                           (const float *)X, stride, nvec, (float *)Y, r.G, r.lg);
     LQ_CHECK_LAUNCH();
 }
 
 } // namespace
+
+extern "C" int lqk_dotprod_route(int kind, unsigned int n, int x_aligned16, unsigned long long nvec,
+                                 unsigned int *blocks, unsigned int *block_cap)
+{
+    if (kind < 0 || kind > 2) return -1;
+    const dot_route r = dotprod_route(kind, n, (long long)n, x_aligned16 != 0, (long long)nvec);
+    if (blocks) *blocks = (unsigned int)r.blocks;
+    if (block_cap) *block_cap = (unsigned int)GRID_CAP;
+    return (r.vec ? 16 : 0) | r.lg;
+}
 
 // one vector, 256 lanes, result straight to pinned host memory + completion
 // flag: the per-call dotprod_*_execute() (one launch, no stream sync)

@@ -49,6 +49,13 @@ void   lqrt_wait_flag(const unsigned *flag, unsigned seq, void *stream);
  * Y[v] = sum_i h[i] X[v*stride + i], v < nvec.  kind: 0 rrrf, 1 crcf, 2 cccf */
 void lqk_dotprod_batch(int kind, const void *h, unsigned int n, const void *X,
                        unsigned long long stride, unsigned long long nvec, void *Y, void *stream);
+/* the launch lqk_dotprod_batch makes for nvec rows of n samples at stride n
+ * (its own decision, no GPU call): bit 4 set for k_dot_vec (n a multiple of
+ * the 16-byte chunk and X 16-byte aligned), clear for k_dot_scalar; bits 0-3
+ * lg G, the lanes per row; *blocks the grid and *block_cap the cap past which
+ * the groups stride over the rows (either may be NULL).  -1: invalid kind */
+int lqk_dotprod_route(int kind, unsigned int n, int x_aligned16, unsigned long long nvec, unsigned int *blocks,
+                      unsigned int *block_cap);
 /* one dot product (dotprod_*_execute): x may be pinned host memory, y is
  * pinned host memory, *flag = seq is raised once y is visible to the host */
 void lqk_dotprod_single(int kind, const void *h, unsigned int n, const void *x, void *y, unsigned *flag,

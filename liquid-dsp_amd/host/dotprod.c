@@ -109,6 +109,28 @@ static void lq_dotprod_execute1(lq_dotprod *q, const void *x, void *y)
 
 lq_ctx *lq_dotprod_ctx(lq_dotprod *q) { return &q->ctx; }
 
+/* the route query of include/liquid_mi355x.h: the launch's own decision */
+_Static_assert(LIQUID_MI355X_DOTPROD_VEC == 16 && LIQUID_MI355X_DOTPROD_LG_MASK == 15, "route codes");
+
+int liquid_mi355x_dotprod_route(int _kind, unsigned int _n, int _x_aligned16, unsigned long long _nvec)
+{
+    return lqk_dotprod_route(_kind, _n, _x_aligned16, _nvec, NULL, NULL);
+}
+
+unsigned int liquid_mi355x_dotprod_blocks(int _kind, unsigned int _n, int _x_aligned16, unsigned long long _nvec)
+{
+    unsigned int blocks = 0;
+    lqk_dotprod_route(_kind, _n, _x_aligned16, _nvec, &blocks, NULL);
+    return blocks;
+}
+
+unsigned int liquid_mi355x_dotprod_block_cap(void)
+{
+    unsigned int cap = 0;
+    lqk_dotprod_route(LQ_RRRF, 1, 1, 1, NULL, &cap);
+    return cap;
+}
+
 /* free functions _run/_run4: one shared scratch object per kind (locked) */
 static pthread_mutex_t g_run_mu = PTHREAD_MUTEX_INITIALIZER;
 static lq_dotprod *g_run[3];

@@ -89,6 +89,35 @@ def firdecim_grid_cap(t, M, hlen, route):
     return int(lib().liquid_mi355x_firdecim_grid_cap(_KINDS[t], M, hlen, FIRDECIM_ROUTES.index(route)))
 
 
+def pinned_input_max():
+    """Bytes of input a host-pointer call stages in pinned memory; more goes by DMA."""
+    return int(lib().liquid_mi355x_pinned_input_max())
+
+
+def copyout_max():
+    """Bytes of result a host-pointer call returns through the copy-out kernel; more goes by DMA."""
+    return int(lib().liquid_mi355x_copyout_max())
+
+
+def dotprod_block_cap():
+    """Grid cap of a dotprod batch launch, in blocks of 256 lanes."""
+    return int(lib().liquid_mi355x_dotprod_block_cap())
+
+
+def dotprod_route(t, n, aligned16=True, nvec=1):
+    """(kernel, G, passes) of a dotprod batch call of nvec rows of n samples
+    (no GPU call), from the launch's own decision: "vec" (k_dot_vec) or
+    "scalar" (k_dot_scalar), the lanes per row, and the passes its grid makes
+    over the rows, ceil(nvec G / (256 blocks))."""
+    a = (_KINDS[t], n, 1 if aligned16 else 0, nvec)
+    r = int(lib().liquid_mi355x_dotprod_route(*a))
+    if r < 0:
+        raise ValueError("dotprod_route: bad arguments")
+    G = 1 << (r & 15)
+    lanes = 256 * int(lib().liquid_mi355x_dotprod_blocks(*a))
+    return "vec" if r & 16 else "scalar", G, -(-nvec * G // lanes)
+
+
 def firinterp_route(t, M, L, aligned16=True):
     """The kernel a firinterp / firpfb device call takes for M phases of L
     taps (no GPU call): 0 the plain kernel, else the register-window kernel's
@@ -617,6 +646,11 @@ def _declare(L):
         "liquid_mi355x_device_synchronize": (None, []),
         "liquid_mi355x_set_max_workgroups": (None, [u]),
         "liquid_mi355x_get_max_workgroups": (u, []),
+        "liquid_mi355x_pinned_input_max": (u, []),
+        "liquid_mi355x_copyout_max": (u, []),
+        "liquid_mi355x_dotprod_route": (i, [i, u, i, ull]),
+        "liquid_mi355x_dotprod_blocks": (u, [i, u, i, ull]),
+        "liquid_mi355x_dotprod_block_cap": (u, []),
         "liquid_mi355x_firdecim_route": (i, [i, u, u, i, ull]),
         "liquid_mi355x_firdecim_tile": (u, [i]),
         "liquid_mi355x_firdecim_grid_cap": (u, [i, u, u, i]),
@@ -872,10 +906,19 @@ class DotProd(_Obj):
         self._fn("_execute")(self.q, ptr(x), ptr(y))
         return y[0]
 
-    def execute_batch(self, X):
+    def recreate(self, h):
+        """dotprod_*_recreate: new coefficients, of any length, on the same object."""
+        self._h = _coefs(h, self.t)
+        self.n = len(self._h)
+        self.q = self._fn("_recreate")(self.q, ptr(self._h), self.n)
+
+    def execute_batch(self, X, nvec=None, fill=0):
+        """nvec: the number of rows where the length does not tell (n = 0);
+        fill: what the result array holds before the call."""
         X = _samples(X, self.t)
-        nvec = X.size // self.n
-        Y = np.zeros(nvec, X.dtype)
+        if nvec is None:
+            nvec = X.size // self.n
+        Y = np.full(nvec, fill, X.dtype)
         self._fn("_execute_batch")(self.q, ptr(X), nvec, ptr(Y))
         return Y
 
@@ -883,12 +926,16 @@ class DotProd(_Obj):
         self._fn("_execute_batch_dev")(self.q, dX, nvec, dY)
 
 
-def dotprod_run(t, h, x):
+def dotprod_run(t, h, x, fn="run"):
     h = _coefs(h, t)
     x = _samples(x, t)
     y = _samples([0], t)
-    getattr(lib(), "dotprod_%s_run" % t)(ptr(h), ptr(x), len(h), ptr(y))
+    getattr(lib(), "dotprod_%s_%s" % (t, fn))(ptr(h), ptr(x), len(h), ptr(y))
     return y[0]
+
+
+def dotprod_run4(t, h, x):
+    return dotprod_run(t, h, x, "run4")
 
 
 def _by_value(v, t):
