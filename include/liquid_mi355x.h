@@ -926,6 +926,48 @@ void firpfbch2_crcf_set_stream(firpfbch2_crcf _q, void *_hip_stream);
 void *firpfbch2_crcf_get_stream(firpfbch2_crcf _q);
 void firpfbch2_crcf_synchronize(firpfbch2_crcf _q);
 
+/* What a channelizer call launches (no reference counterpart; for tests).
+ * The answer is the launch's own decision: the launches call the same host
+ * functions.  No GPU call is made.  Returns the route, an index into
+ * liquid_mi355x_channelizer_route_name(0 .. liquid_mi355x_channelizer_route_count() - 1),
+ * or -1 for arguments no object can have (and a size the GPU path refuses).
+ * A route is one kernel family plus what a test must tell apart: paired or
+ * 8-byte input loads (`_unpaired'), the few-block form and its signalling
+ * variant, real or complex taps (`_c'); DESIGN.md has the table.
+ *   _type: LIQUID_ANALYZER / LIQUID_SYNTHESIZER; _kind: 1 crcf, 2 cccf;
+ *   _first_block_parity: blocks the object has run so far, mod 2;
+ *   _x_aligned16 / _y_aligned16: the device pointers' alignment (8 bytes is
+ *     taken as given);
+ *   _host_call: the call comes through execute_block on host pointers, which
+ *     tries the signalling few-block launch when the output fits the pinned
+ *     completion buffer (liquid_mi355x_copyout_max());
+ *   *_run: blocks one workgroup (or one of its column sets) walks;
+ *   *_workgroups: the grid (of the filter kernel where a batched transform
+ *     goes with it); both of the call's first launch;
+ *   *_chunks: launches the call is cut into.  Any of the three may be NULL.
+ * The queries answer as the launches do under LQ_PFB2_TWO_PASS /
+ * LQ_PFB_TWO_PASS, liquid_mi355x_set_max_workgroups and
+ * liquid_mi355x_set_channelizer_chunk. */
+int liquid_mi355x_firpfbch2_route(int _type, unsigned int _M, unsigned int _m, unsigned long long _nblocks,
+                                  int _first_block_parity, int _x_aligned16, int _y_aligned16, int _host_call,
+                                  unsigned long long *_run, unsigned long long *_workgroups,
+                                  unsigned long long *_chunks);
+int liquid_mi355x_firpfbch_route(int _kind, int _type, unsigned int _M, unsigned int _p, unsigned long long _nblocks,
+                                 int _x_aligned16, int _y_aligned16, int _host_call, unsigned long long *_run,
+                                 unsigned long long *_workgroups, unsigned long long *_chunks);
+int liquid_mi355x_channelizer_route_count(void);
+const char *liquid_mi355x_channelizer_route_name(int _i);
+/* tests only: blocks per launch of the analyzers that cut a long call into
+ * chunks (firpfbch2 at M >= 64 a power of two, firpfbch at M = 1024 with 4 or
+ * 8 real taps per branch).  0 (default): 2^27 / M, 2^18 and 2^17 blocks.
+ * Refused (-1, nothing changes): values below 64 or no multiple of 32 -- the
+ * block parity is carried per chunk, the M = 1024 kernels count groups of 16
+ * blocks from the absolute block index, and a later chunk takes its history
+ * from the input before it (at most 31 blocks).  A value past the default
+ * leaves the default.  Results do not depend on it.  Process-wide. */
+int liquid_mi355x_set_channelizer_chunk(unsigned long long _blocks);
+unsigned long long liquid_mi355x_get_channelizer_chunk(void);
+
 /* ------------------------------------------------------------------------ */
 /* nco (liquid.h:5919-5999): crcf                                            */
 /* ------------------------------------------------------------------------ */

@@ -204,15 +204,10 @@ __global__ __launch_bounds__(256 * R, R == 1 ? 2 : 1) void k_pfb_an_fused(const 
 }
 
 template <typename TC>
-bool launch_pfb_an_fused(int M, int p, const void *hsub, const void *hist, const void *x, long long nb, void *Y,
-                         hipStream_t st)
+void launch_pfb_an_fused(int M, int p, const void *hsub, const void *hist, const void *x, long long nb, void *Y,
+                         long long S, unsigned grid, hipStream_t st)
 {
-    if ((M != 256 && M != 512) || nb * (long long)M * 8 >= (1ll << 31)) return false;
-    long long S = (nb + 1023) / 1024;
-    S = (S + 15) / 16 * 16;
-    if (S < 32) S = 32;
-    const unsigned grid = (unsigned)((nb + S - 1) / S);
-    return lq_switch<2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
+    lq_switch<2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
         lq_switch<256, 512>(M, [&](auto MM) {
             hipLaunchKernelGGL((k_pfb_an_fused<P, TC, MM / 256>), dim3(grid), dim3(MM), 0, st, (const TC *)hsub,
                                (const float2 *)hist, (const float2 *)x, (int)(nb * M), (int)nb, (int)S,
@@ -336,16 +331,11 @@ __global__ __launch_bounds__(1024, 1) void k_pfb_an4096(const TC *__restrict__ h
 }
 
 template <typename TC>
-bool launch_pfb_an4096(int p, const void *hsub, const void *hist, const void *x, long long nb, void *Y,
-                       hipStream_t st)
+void launch_pfb_an4096(int p, const void *hsub, const void *hist, const void *x, long long nb, void *Y, long long S,
+                       unsigned grid, hipStream_t st)
 {
     constexpr int M = 4096;
-    if (nb * (long long)M * 8 >= (1ll << 31)) return false;
-    // one workgroup per CU: about 256 runs of S blocks (each warms up on the p - 1 rows before it)
-    long long S = (nb + 255) / 256;
-    if (S < 32) S = 32;
-    const unsigned grid = (unsigned)((nb + S - 1) / S);
-    return lq_switch<2, 4, 6, 8>(p, [&](auto P) {
+    lq_switch<2, 4, 6, 8>(p, [&](auto P) {
         hipLaunchKernelGGL((k_pfb_an4096<P, TC>), dim3(grid), dim3(1024), 0, st, (const TC *)hsub,
                            (const float2 *)hist, (const float2 *)x, (int)(nb * M), (int)nb, (int)S, (float2 *)Y,
                            (const float2 *)lqrt_twiddles());
@@ -419,17 +409,10 @@ __global__ __launch_bounds__(256, 2) void k_pfb_an_small(const TC *__restrict__ 
 }
 
 template <typename TC>
-bool launch_pfb_an_small(int M, int p, const void *hsub, const void *hist, const void *x, long long nb, void *Y,
-                         hipStream_t st)
+void launch_pfb_an_small(int M, int p, const void *hsub, const void *hist, const void *x, long long nb, void *Y,
+                         long long S, unsigned grid, hipStream_t st)
 {
-    if ((M != 64 && M != 128) || nb * (long long)M * 8 >= (1ll << 31)) return false;
-    const int Q = 256 / M;
-    long long S = (nb + 2047) / 2048;
-    S = (S + 15) / 16 * 16;
-    if (S < 32) S = 32;
-    const long long nseg = (nb + S - 1) / S;
-    const unsigned grid = (unsigned)((nseg + Q - 1) / Q);
-    return lq_switch<2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
+    lq_switch<2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
         lq_switch<64, 128>(M, [&](auto MM) {
             hipLaunchKernelGGL((k_pfb_an_small<P, TC, MM>), dim3(grid), dim3(256), 0, st, (const TC *)hsub,
                                (const float2 *)hist, (const float2 *)x, (int)(nb * M), (int)nb, (int)S,
@@ -511,15 +494,10 @@ __global__ __launch_bounds__(256 * R, R == 1 ? 2 : 1) void k_pfb_syn_fused(const
 }
 
 template <typename TC>
-bool launch_pfb_syn_fused(int M, int p, const void *hsub, const void *state, const void *X, long long nb, void *y,
-                          void *znew, hipStream_t st)
+void launch_pfb_syn_fused(int M, int p, const void *hsub, const void *state, const void *X, long long nb, void *y,
+                          void *znew, long long S, unsigned grid, hipStream_t st)
 {
-    if ((M != 256 && M != 512) || p > 16 || nb < p || nb * (long long)M >= (1ll << 31)) return false;
-    long long S = (nb + 1023) / 1024;
-    S = (S + 15) / 16 * 16;
-    if (S < 64) S = 64;
-    const unsigned grid = (unsigned)((nb + S - 1) / S);
-    return lq_switch<2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
+    lq_switch<2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
         lq_switch<256, 512>(M, [&](auto MM) {
             hipLaunchKernelGGL((k_pfb_syn_fused<P, TC, MM / 256>), dim3(grid), dim3(MM), 0, st, (const TC *)hsub,
                                (const float2 *)state, (const float2 *)X, (int)nb, (int)S, (float2 *)y,
@@ -648,16 +626,10 @@ __global__ __launch_bounds__(1024, 1) void k_pfb_syn4096(const TC *__restrict__ 
 }
 
 template <typename TC>
-bool launch_pfb_syn4096(int p, const void *hsub, const void *state, const void *X, long long nb, void *y, void *znew,
-                        hipStream_t st)
+void launch_pfb_syn4096(int p, const void *hsub, const void *state, const void *X, long long nb, void *y, void *znew,
+                        long long S, unsigned grid, hipStream_t st)
 {
-    constexpr int M = 4096;
-    if (nb < p || nb * (long long)M * 8 >= (1ll << 31)) return false;
-    long long S = (nb + 255) / 256;
-    S = (S + 2) / 3 * 3;
-    if (S < 33) S = 33;
-    const unsigned grid = (unsigned)((nb + S - 1) / S);
-    return lq_switch<2, 4, 6, 8>(p, [&](auto P) {
+    lq_switch<2, 4, 6, 8>(p, [&](auto P) {
         hipLaunchKernelGGL((k_pfb_syn4096<P, TC>), dim3(grid), dim3(1024), 0, st, (const TC *)hsub,
                            (const float2 *)state, (const float2 *)X, (int)nb, (int)S, (float2 *)y,
                            (float2 *)znew, (const float2 *)lqrt_twiddles());
@@ -729,17 +701,10 @@ __global__ __launch_bounds__(256, 2) void k_pfb_syn_small(const TC *__restrict__
 }
 
 template <typename TC>
-bool launch_pfb_syn_small(int M, int p, const void *hsub, const void *state, const void *X, long long nb, void *y,
-                          void *znew, hipStream_t st)
+void launch_pfb_syn_small(int M, int p, const void *hsub, const void *state, const void *X, long long nb, void *y,
+                          void *znew, long long S, unsigned grid, hipStream_t st)
 {
-    if ((M != 64 && M != 128) || p > 16 || nb < p || nb * (long long)M >= (1ll << 31)) return false;
-    const int Q = 256 / M;
-    long long S = (nb + 2047) / 2048;
-    S = (S + 15) / 16 * 16;
-    if (S < 64) S = 64;
-    const long long nseg = (nb + S - 1) / S;
-    const unsigned grid = (unsigned)((nseg + Q - 1) / Q);
-    return lq_switch<2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
+    lq_switch<2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
         lq_switch<64, 128>(M, [&](auto MM) {
             hipLaunchKernelGGL((k_pfb_syn_small<P, TC, MM>), dim3(grid), dim3(256), 0, st, (const TC *)hsub,
                                (const float2 *)state, (const float2 *)X, (int)nb, (int)S, (float2 *)y,
@@ -749,31 +714,7 @@ bool launch_pfb_syn_small(int M, int p, const void *hsub, const void *state, con
     });
 }
 
-// dispatch helpers: compile-time ring depths for the common shapes, else the
-// per-element kernels
-template <typename TC>
-bool launch_an_X_run(int M, int p, const void *hsub, const void *hist, const void *x, long long nb, void *X,
-                     hipStream_t st)
-{
-    const long long threads = (long long)M * ((nb + RUN - 1) / RUN);
-    const dim3 g((unsigned)((threads + 255) / 256));
-    return lq_switch<1, 2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
-        hipLaunchKernelGGL((k_pfb_an_X_run<P, TC>), g, dim3(256), 0, st, M, (const TC *)hsub, (const float2 *)hist,
-                           (const float2 *)x, nb, (float2 *)X);
-    });
-}
-
-template <typename TC>
-bool launch_syn_run(int M, int p, const void *hsub, const void *Z, long long nb, void *y, hipStream_t st)
-{
-    const long long threads = (long long)M * ((nb + RUN - 1) / RUN);
-    const dim3 g((unsigned)((threads + 255) / 256));
-    return lq_switch<1, 2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
-        hipLaunchKernelGGL((k_pfb_syn_out_run<P, TC>), g, dim3(256), 0, st, M, (const TC *)hsub, (const float2 *)Z,
-                           nb, (float2 *)y);
-    });
-}
-
+// ------------------------------------------------------------------ what a launch decides
 // Diagnostic switch (DESIGN.md (a) history): LQ_PFB_TWO_PASS in the
 // environment routes the fused sizes through the generic two-pass path.
 // Read once per process.
@@ -783,19 +724,87 @@ bool pfb_two_pass()
     return v;
 }
 
-// The routing order behind the M = 1024 fast paths, for taps of type TC
+long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+
+// runs of S blocks, a multiple of `step' and at least `least', over about T
+// workgroups (or column sets): T is lqrt_grid(N, N), N itself unless
+// liquid_mi355x_set_max_workgroups has set a lower limit (tests only)
+long long blocks_run(long long nb, unsigned N, long long step, long long least)
+{
+    const long long S = cdiv(cdiv(nb, lqrt_grid(N, N)), step) * step;
+    return S < least ? least : S;
+}
+
+bool even_to(unsigned p, unsigned top) { return p >= 2 && p <= top && p % 2 == 0; }   // lq_switch<2, 4, .., top>
+
+// The routing order behind the M = 1024 fast paths (k_pfb2_fast.hip).  The
+// route of complex taps is its real one + 1.
+lqk_pfb_plan pfb_an_plan(int ctaps, unsigned M, unsigned p, long long nb)
+{
+    const lqk_pfb_plan none = {LQK_PFB_NONE, 0, 0, 1};
+    if (M < 1 || p < 1 || nb < 1) return none;
+    const int c = ctaps ? 1 : 0;
+    const bool fused = !pfb_two_pass() && nb * (long long)M * 8 < (1ll << 31);   // 32-bit buffer offsets
+    if (fused && (M == 256 || M == 512) && even_to(p, 16)) {
+        const long long S = blocks_run(nb, 1024, 16, 32);
+        return {LQK_PFB_AN_FUSED + c, S, cdiv(nb, S), 1};
+    }
+    if (fused && M == 4096 && even_to(p, 8)) {
+        // one workgroup per CU: about 256 runs of S blocks (each warms up on the p - 1 rows before it)
+        const long long S = blocks_run(nb, 256, 1, 32);
+        return {LQK_PFB_AN4096 + c, S, cdiv(nb, S), 1};
+    }
+    if (fused && (M == 64 || M == 128) && even_to(p, 16)) {
+        const long long S = blocks_run(nb, 2048, 16, 32);
+        return {LQK_PFB_AN_SMALL + c, S, cdiv(cdiv(nb, S), 256 / M), 1};
+    }
+    // X is formed in Y then transformed in place: compile-time ring depths
+    // for the common shapes, else the per-element kernel
+    if (p == 1 || even_to(p, 16)) return {LQK_PFB_AN_RUN_FFT + c, RUN, cdiv((long long)M * cdiv(nb, RUN), 256), 1};
+    return {LQK_PFB_AN_ELEM_FFT + c, 1, cdiv(nb * M, 256), 1};
+}
+
+lqk_pfb_plan pfb_syn_plan(int ctaps, unsigned M, unsigned p, long long nb)
+{
+    const lqk_pfb_plan none = {LQK_PFB_NONE, 0, 0, 1};
+    if (M < 1 || p < 1 || nb < 1) return none;
+    const int c = ctaps ? 1 : 0;
+    const bool fused = !pfb_two_pass() && nb >= (long long)p;
+    if (fused && (M == 256 || M == 512) && even_to(p, 16) && nb * (long long)M < (1ll << 31)) {
+        const long long S = blocks_run(nb, 1024, 16, 64);
+        return {LQK_PFB_SYN_FUSED + c, S, cdiv(nb, S), 1};
+    }
+    if (fused && M == 4096 && even_to(p, 8) && nb * (long long)M * 8 < (1ll << 31)) {
+        const long long S = blocks_run(nb, 256, 3, 33);
+        return {LQK_PFB_SYN4096 + c, S, cdiv(nb, S), 1};
+    }
+    if (fused && (M == 64 || M == 128) && even_to(p, 16) && nb * (long long)M < (1ll << 31)) {
+        const long long S = blocks_run(nb, 2048, 16, 64);
+        return {LQK_PFB_SYN_SMALL + c, S, cdiv(cdiv(nb, S), 256 / M), 1};
+    }
+    if (p == 1 || even_to(p, 16)) return {LQK_PFB_FFT_SYN_RUN + c, RUN, cdiv((long long)M * cdiv(nb, RUN), 256), 1};
+    return {LQK_PFB_FFT_SYN_ELEM + c, 1, cdiv(nb * M, 256), 1};
+}
+
 template <typename TC>
 void pfb_analyzer(int M, int p, const void *hsub, const void *hist, const void *x, long long nb, void *Y,
                   hipStream_t st)
 {
-    if (!pfb_two_pass() && launch_pfb_an_fused<TC>(M, p, hsub, hist, x, nb, Y, st)) return;
-    if (M == 4096 && !pfb_two_pass() && launch_pfb_an4096<TC>(p, hsub, hist, x, nb, Y, st)) return;
-    if (!pfb_two_pass() && launch_pfb_an_small<TC>(M, p, hsub, hist, x, nb, Y, st)) return;
-    // X is formed in Y then transformed in place
-    if (!launch_an_X_run<TC>(M, p, hsub, hist, x, nb, Y, st)) {
-        const long long tot = nb * M;
-        hipLaunchKernelGGL(k_pfb_an_X<TC>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, M, p,
-                           (const TC *)hsub, (const float2 *)hist, (const float2 *)x, nb, (float2 *)Y);
+    const lqk_pfb_plan pl = pfb_an_plan(sizeof(TC) == sizeof(float2), M, p, nb);
+    const unsigned grid = (unsigned)pl.workgroups;
+    switch (pl.route - ((pl.route - LQK_PFB_AN_FUSED) & 1)) {   // the real-tap code
+    case LQK_PFB_AN_FUSED: launch_pfb_an_fused<TC>(M, p, hsub, hist, x, nb, Y, pl.run, grid, st); return;
+    case LQK_PFB_AN4096: launch_pfb_an4096<TC>(p, hsub, hist, x, nb, Y, pl.run, grid, st); return;
+    case LQK_PFB_AN_SMALL: launch_pfb_an_small<TC>(M, p, hsub, hist, x, nb, Y, pl.run, grid, st); return;
+    case LQK_PFB_AN_RUN_FFT:
+        lq_switch<1, 2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
+            hipLaunchKernelGGL((k_pfb_an_X_run<P, TC>), dim3(grid), dim3(256), 0, st, M, (const TC *)hsub,
+                               (const float2 *)hist, (const float2 *)x, nb, (float2 *)Y);
+        });
+        break;
+    default:
+        hipLaunchKernelGGL(k_pfb_an_X<TC>, dim3(grid), dim3(256), 0, st, M, p, (const TC *)hsub,
+                           (const float2 *)hist, (const float2 *)x, nb, (float2 *)Y);
     }
     LQ_CHECK_LAUNCH();
     lq_fft_batch_scaled(M, +1, Y, Y, nb, 1.f, 1.f, 0, 0, st);
@@ -808,26 +817,49 @@ void pfb_synthesizer(int M, int p, const void *hsub, void *state, void *zscratch
     const long long HB = (long long)p - 1;
     const size_t hbytes = HB * M * sizeof(float2);
     float2 *Z = (float2 *)zscratch;
+    const lqk_pfb_plan pl = pfb_syn_plan(sizeof(TC) == sizeof(float2), M, p, nb);
+    const unsigned grid = (unsigned)pl.workgroups;
+    const int route = pl.route - ((pl.route - LQK_PFB_SYN_FUSED) & 1);   // the real-tap code
     // fused forms: the last p-1 transforms land in the scratch, then become
     // the state (every workgroup reads the old state first)
-    if ((!pfb_two_pass() && launch_pfb_syn_fused<TC>(M, p, hsub, state, X, nb, y, Z, st)) ||
-        (M == 4096 && !pfb_two_pass() && launch_pfb_syn4096<TC>(p, hsub, state, X, nb, y, Z, st)) ||
-        (!pfb_two_pass() && launch_pfb_syn_small<TC>(M, p, hsub, state, X, nb, y, Z, st))) {
+    if (route == LQK_PFB_SYN_FUSED || route == LQK_PFB_SYN4096 || route == LQK_PFB_SYN_SMALL) {
+        if (route == LQK_PFB_SYN_FUSED)
+            launch_pfb_syn_fused<TC>(M, p, hsub, state, X, nb, y, Z, pl.run, grid, st);
+        else if (route == LQK_PFB_SYN4096)
+            launch_pfb_syn4096<TC>(p, hsub, state, X, nb, y, Z, pl.run, grid, st);
+        else
+            launch_pfb_syn_small<TC>(M, p, hsub, state, X, nb, y, Z, pl.run, grid, st);
         if (HB > 0) LQ_CHECK(hipMemcpyAsync(state, Z, hbytes, hipMemcpyDeviceToDevice, st));
         return;
     }
     if (HB > 0) LQ_CHECK(hipMemcpyAsync(Z, state, hbytes, hipMemcpyDeviceToDevice, st));
     lq_fft_batch_scaled(M, -1, X, Z + HB * M, nb, 1.f, 1.f, 0, 0, st);
-    if (!launch_syn_run<TC>(M, p, hsub, Z, nb, y, st)) {
-        const long long tot = nb * M;
-        hipLaunchKernelGGL(k_pfb_syn_out<TC>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, M, p,
-                           (const TC *)hsub, (const float2 *)Z, nb, (float2 *)y);
-    }
+    if (route == LQK_PFB_FFT_SYN_RUN)
+        lq_switch<1, 2, 4, 6, 8, 10, 12, 14, 16>(p, [&](auto P) {
+            hipLaunchKernelGGL((k_pfb_syn_out_run<P, TC>), dim3(grid), dim3(256), 0, st, M, (const TC *)hsub,
+                               (const float2 *)Z, nb, (float2 *)y);
+        });
+    else
+        hipLaunchKernelGGL(k_pfb_syn_out<TC>, dim3(grid), dim3(256), 0, st, M, p, (const TC *)hsub,
+                           (const float2 *)Z, nb, (float2 *)y);
     LQ_CHECK_LAUNCH();
     if (HB > 0) LQ_CHECK(hipMemcpyAsync(state, Z + nb * M, hbytes, hipMemcpyDeviceToDevice, st));
 }
 
 } // namespace
+
+extern "C" lqk_pfb_plan lqk_firpfbch_plan(int analyzer, int ctaps, unsigned int M, unsigned int p,
+                                          unsigned long long nblocks, int x16, int y16, int signal)
+{
+    const lqk_pfb_plan none = {LQK_PFB_NONE, 0, 0, 1};
+    if (nblocks == 0 || nblocks > (1ull << 40) || M == 0 || M > (1u << 20) || p == 0 || p > (1u << 10)) return none;
+    lqk_pfb_plan pl = lqk_pfb_fast_plan(analyzer, ctaps, M, p, nblocks, x16, y16, signal);
+    // (a signalling call the few-block kernel does not take goes on as a device call)
+    if (pl.route == LQK_PFB_NONE && analyzer && signal)
+        pl = lqk_pfb_fast_plan(1, ctaps, M, p, nblocks, x16, y16, 0);
+    if (pl.route != LQK_PFB_NONE) return pl;
+    return analyzer ? pfb_an_plan(ctaps, M, p, (long long)nblocks) : pfb_syn_plan(ctaps, M, p, (long long)nblocks);
+}
 
 extern "C" void lqk_firpfbch_analyzer(int ctaps, unsigned int M, unsigned int p, const void *hsub, const void *hist,
                                       const void *x, unsigned long long nblocks, void *Y, void *stream)

@@ -262,28 +262,17 @@ __global__ __launch_bounds__(256 * R, R == 1 ? 2 : 1) void k_pfb2_an256(const fl
 }
 
 template <int L, int R>
-bool launch_pfb2_an256(const void *hsub, const void *hist, const void *x, long long nb, int p0, void *Y, hipStream_t st)
+void launch_pfb2_an256(const void *hsub, const void *hist, const void *x, long long nb, int p0, void *Y, long long S,
+                       long long nseg, hipStream_t st)
 {
     constexpr int M = 256 * R;
     const long long n_in = nb * (M / 2);
-    if (n_in * 8 >= (1ll << 31) || nb * (long long)M * 8 >= (1ll << 31)) return false;
     const int cmin = (p0 - 1) >> 1;
     const int cmax = (int)((p0 + nb - 1) >> 1);
-    const int rows = cmax - cmin + 1;
-    // runs of S rows (a multiple of 8): about 1024 workgroups on long calls
-    // (a remainder of a few rows goes to one short extra run, as in
-    // launch_pfb2_an2048)
-    long long S = ((long long)rows + 1023) / 1024;
-    S = (S + 7) / 8 * 8;
-    const long long S8 = (long long)rows / 8192 * 8;
-    if (S8 >= 32 && rows - 1024 * S8 <= S8 / 4) S = S8;
-    if (S < 32) S = 32;
-    const long long nseg = (rows + S - 1) / S;
     hipLaunchKernelGGL((k_pfb2_an256<L, R>), dim3((unsigned)nseg), dim3(256 * R), 0, st, (const float *)hsub,
                        (const float2 *)hist, (const float2 *)x, (int)n_in, p0, (int)nb, cmin, cmax, (int)S,
                        (float2 *)Y, (const float2 *)lqrt_twiddles());
     LQ_CHECK_LAUNCH();
-    return true;
 }
 
 // M = 2048 analyzer fused (the two-pass path moved 56 B per input): 1024
@@ -433,29 +422,17 @@ __global__ __launch_bounds__(1024, 1) void k_pfb2_an2048(const float *__restrict
 }
 
 template <int L>
-bool launch_pfb2_an2048(const void *hsub, const void *hist, const void *x, long long nb, int p0, void *Y, hipStream_t st)
+void launch_pfb2_an2048(const void *hsub, const void *hist, const void *x, long long nb, int p0, void *Y, long long S,
+                        long long nseg, hipStream_t st)
 {
     constexpr int M = 2048;
     const long long n_in = nb * (M / 2);
-    if (n_in * 8 >= (1ll << 31) || nb * (long long)M * 8 >= (1ll << 31)) return false;
     const int cmin = (p0 - 1) >> 1;
     const int cmax = (int)((p0 + nb - 1) >> 1);
-    const int rows = cmax - cmin + 1;
-    // one workgroup per CU: runs of S rows (a multiple of 8), about 256 runs.
-    // A remainder of a few rows past 256 full runs goes to one short extra
-    // run rather than stretching every run to the next multiple of 8 (2^27
-    // inputs: 65 537 rows, 256 x 256 + 1 instead of 249 x 264 -- 7 CUs idle)
-    long long S = ((long long)rows + 255) / 256;
-    S = (S + 7) / 8 * 8;
-    const long long S8 = (long long)rows / 2048 * 8;
-    if (S8 >= 32 && rows - 256 * S8 <= S8 / 4) S = S8;
-    if (S < 32) S = 32;
-    const long long nseg = (rows + S - 1) / S;
     hipLaunchKernelGGL((k_pfb2_an2048<L>), dim3((unsigned)nseg), dim3(1024), 0, st, (const float *)hsub,
                        (const float2 *)hist, (const float2 *)x, (int)n_in, p0, (int)nb, cmin, cmax, (int)S,
                        (float2 *)Y, (const float2 *)lqrt_twiddles());
     LQ_CHECK_LAUNCH();
-    return true;
 }
 
 // M = 4096 analyzer fused (the two-pass path moved 56 B per input; the
@@ -685,24 +662,17 @@ __global__ __launch_bounds__(1024, 1) void k_pfb2_an4096(const float *__restrict
 }
 
 template <int L>
-bool launch_pfb2_an4096(const void *hsub, const void *hist, const void *x, long long nb, int p0, void *Y, hipStream_t st)
+void launch_pfb2_an4096(const void *hsub, const void *hist, const void *x, long long nb, int p0, void *Y, long long S,
+                        long long nseg, hipStream_t st)
 {
     constexpr int M = 4096;
     const long long n_in = nb * (M / 2);
-    if (n_in * 8 >= (1ll << 31) || nb * (long long)M * 8 >= (1ll << 31)) return false;
     const int cmin = (p0 - 1) >> 1;
     const int cmax = (int)((p0 + nb - 1) >> 1);
-    const int rows = cmax - cmin + 1;
-    // one workgroup per CU: runs of S rows, about 256 runs (each warms up on
-    // the 2m rows before it)
-    long long S = ((long long)rows + 255) / 256;
-    if (S < 32) S = 32;
-    const long long nseg = (rows + S - 1) / S;
     hipLaunchKernelGGL((k_pfb2_an4096<L>), dim3((unsigned)nseg), dim3(1024), 0, st, (const float *)hsub,
                        (const float2 *)hist, (const float2 *)x, (int)n_in, p0, (int)nb, cmin, cmax, (int)S,
                        (float2 *)Y, (const float2 *)lqrt_twiddles());
     LQ_CHECK_LAUNCH();
-    return true;
 }
 
 // M = 64 / 128 analyzer fused (the two-pass path moved 56 B per input): as
@@ -812,52 +782,32 @@ __global__ __launch_bounds__(256, 2) void k_pfb2_an_small(const float *__restric
 }
 
 template <int L, int MS>
-bool launch_pfb2_an_small(const void *hsub, const void *hist, const void *x, long long nb, int p0, void *Y,
-                          hipStream_t st)
+void launch_pfb2_an_small(const void *hsub, const void *hist, const void *x, long long nb, int p0, void *Y,
+                          long long S, long long nwg, hipStream_t st)
 {
-    constexpr int M = MS, Q = 256 / M;
+    constexpr int M = MS;
     const long long n_in = nb * (M / 2);
-    if (n_in * 8 >= (1ll << 31) || nb * (long long)M * 8 >= (1ll << 31)) return false;
     const int cmin = (p0 - 1) >> 1;
     const int cmax = (int)((p0 + nb - 1) >> 1);
-    const int rows = cmax - cmin + 1;
-    // runs of S rows (a multiple of 8) per set: about 2048 sets on long calls
-    // (no short extra run here: every set of a workgroup runs the same
-    // number of groups, so an extra workgroup costs a whole run -- measured
-    // 0.83 -> 1.07 ms at M = 64, r05zo)
-    long long S = ((long long)rows + 2047) / 2048;
-    S = (S + 7) / 8 * 8;
-    if (S < 32) S = 32;
-    const long long nseg = (rows + S - 1) / S;
-    const long long nwg = (nseg + Q - 1) / Q;
     hipLaunchKernelGGL((k_pfb2_an_small<L, MS>), dim3((unsigned)nwg), dim3(256), 0, st, (const float *)hsub,
                        (const float2 *)hist, (const float2 *)x, (int)n_in, p0, (int)nb, cmin, cmax, (int)S,
                        (float2 *)Y, (const float2 *)lqrt_twiddles());
     LQ_CHECK_LAUNCH();
-    return true;
 }
 
 template <int L>
-bool launch_pfb2_poly(int M, const void *hsub, const void *hist, const void *x, long long nb, int p0, void *Y,
-                      hipStream_t st)
+void launch_pfb2_poly(int M, const void *hsub, const void *hist, const void *x, long long nb, int p0, void *Y,
+                      long long S, long long nwg, hipStream_t st)
 {
     const long long n_in = nb * (M / 2);
-    if (n_in * 8 >= (1ll << 31) || nb * (long long)M * 8 >= (1ll << 31)) return false;   // 32-bit buffer offsets
     const int cmin = (p0 - 1) >> 1;                            // floor((p0 - 1) / 2)
     const int cmax = (int)((p0 + nb - 1) >> 1);
-    const int rows = cmax - cmin + 1;
     const int nt = M < 256 ? M : 256;
     const int nsl = M / nt;
-    // runs of S rows: >= 2048 workgroups when the call is long, and runs of
-    // at least 4L rows so the L-1 warm-up rows stay a small overhead
-    long long S = ((long long)rows * nsl + 2047) / 2048;
-    if (S < 4 * L) S = 4 * L;
-    const long long nseg = (rows + S - 1) / S;
-    hipLaunchKernelGGL((k_pfb2_poly<L>), dim3((unsigned)(nseg * nsl)), dim3(nt), 0, st, M, nsl, (const float *)hsub,
+    hipLaunchKernelGGL((k_pfb2_poly<L>), dim3((unsigned)nwg), dim3(nt), 0, st, M, nsl, (const float *)hsub,
                        (const float2 *)hist, (const float2 *)x, (int)n_in, p0, (int)nb, cmin, cmax, (int)S,
                        (float2 *)Y, (const float2 *)lqrt_zeros());
     LQ_CHECK_LAUNCH();
-    return true;
 }
 
 // generic even M (not a power of two): direct O(M^2) DFT, one workgroup per block
@@ -1197,53 +1147,11 @@ __global__ __launch_bounds__(1024, 1) void k_pfb2_syn4096(const float *__restric
     }
 }
 
-template <int L>
-bool launch_pfb2_syn4096_l(const void *hsub, const void *state, const void *X, long long nb, int p0, void *y,
-                           void *znew, hipStream_t st)
-{
-    long long S = (nb + 255) / 256;   // about 256 runs (one workgroup per CU), whole groups of three
-    S = (S + 2) / 3 * 3;
-    if (S < 33) S = 33;
-    const unsigned grid = (unsigned)((nb + S - 1) / S);
-    hipLaunchKernelGGL((k_pfb2_syn4096<L>), dim3(grid), dim3(1024), 0, st, (const float *)hsub, (const float2 *)state,
-                       (const float2 *)X, (int)nb, p0, (int)S, (float2 *)y, (float2 *)znew,
-                       (const float2 *)lqrt_twiddles());
-    LQ_CHECK_LAUNCH();
-    return true;
-}
-
-bool launch_pfb2_syn4096(int m, const void *hsub, const void *state, const void *X, long long nb, int p0, void *y,
-                         void *znew, hipStream_t st)
-{
-    if (m < 1 || m > 4 || nb < 4 * m - 1 || nb * 4096ll * 8 >= (1ll << 31)) return false;
-    return lq_switch<2, 4, 6, 8>(2 * m,
-                                 [&](auto L) { launch_pfb2_syn4096_l<L>(hsub, state, X, nb, p0, y, znew, st); });
-}
-
-bool launch_pfb2_syn_fused(int M, int m, const void *hsub, const void *state, const void *X, long long nb, int p0,
-                           void *y, void *znew, hipStream_t st)
-{
-    if ((M != 256 && M != 512) || m < 1 || m > 4 || nb < 16 || nb * (long long)M >= (1ll << 31)) return false;
-    long long S = (nb + 1023) / 1024;
-    S = (S + 15) / 16 * 16;
-    if (S < 64) S = 64;
-    const unsigned grid = (unsigned)((nb + S - 1) / S);
-    return lq_switch<2, 4, 6, 8>(2 * m, [&](auto L) {
-        lq_switch<256, 512>(M, [&](auto MM) {
-            hipLaunchKernelGGL((k_pfb2_syn_fused<L, MM / 256>), dim3(grid), dim3(MM), 0, st, (const float *)hsub,
-                               (const float2 *)state, (const float2 *)X, (int)nb, p0, (int)S, (float2 *)y,
-                               (float2 *)znew, (const float2 *)lqrt_twiddles());
-        });
-        LQ_CHECK_LAUNCH();
-    });
-}
-
 template <int M>
 void launch_pfb2_an(int m, const void *hsub, const void *hist, const void *x, long long nblocks, int p0, void *Y,
-                    hipStream_t st)
+                    long long grid, hipStream_t st)
 {
     constexpr int NB = M >= 1024 ? 1 : 1024 / M;
-    const long long grid = (nblocks + NB - 1) / NB;
     hipLaunchKernelGGL((k_pfb2_an<M, NB>), dim3((unsigned)grid), dim3(NT), 0, st, m, (const float *)hsub,
                        (const float2 *)hist, (const float2 *)x, nblocks, p0, (float2 *)Y,
                        (const float2 *)lqrt_twiddles());
@@ -1261,7 +1169,149 @@ bool pfb2_two_pass()
     return v;
 }
 
+// ------------------------------------------------------------------ what a launch decides
+// The launches below and lqk_firpfbch2_plan (the route query) both call
+// these.  The workgroup targets N ("about N workgroups on long calls") are
+// lqrt_grid(N, N): N itself unless liquid_mi355x_set_max_workgroups has set a
+// lower limit, which lengthens the runs (tests only).
+long long cdiv(long long a, long long b) { return (a + b - 1) / b; }
+
+// runs of S rows, a multiple of 8 and at least 32, over about T workgroups.
+// A remainder of a few rows past T full runs goes to one short extra run
+// rather than stretching every run to the next multiple of 8 (M = 2048, 2^27
+// inputs: 65 537 rows, 256 x 256 + 1 instead of 249 x 264 -- 7 CUs idle)
+long long rows_run8(long long rows, long long T, bool extra)
+{
+    long long S = cdiv(cdiv(rows, T), 8) * 8;
+    const long long S8 = rows / (8 * T) * 8;
+    if (extra && S8 >= 32 && rows - T * S8 <= S8 / 4) S = S8;
+    return S < 32 ? 32 : S;
+}
+
+constexpr bool pfb2_direct_size(unsigned M)
+{
+    return M == 2 || M == 4 || M == 8 || M == 16 || M == 32 || M == 64 || M == 128 || M == 256 || M == 512 ||
+           M == 1024 || M == 2048 || M == 4096;
+}
+
+// one launch (chunk) of the analyzer at a size with a polyphase form
+// (M >= 64 a power of two, 2m <= 16): nb blocks from parity p0.  run is in
+// blocks (two per row of the polyphase matrix).
+lqk_pfb_plan pfb2_an_chunk(unsigned M, unsigned m, long long nb, int p0)
+{
+    const lqk_pfb_plan none = {LQK_PFB_NONE, 0, 0, 1};
+    const long long n_in = nb * (M / 2);
+    if (n_in * 8 >= (1ll << 31) || nb * (long long)M * 8 >= (1ll << 31)) return none;   // 32-bit buffer offsets
+    const long long cmin = (p0 - 1) >> 1;                      // floor((p0 - 1) / 2)
+    const long long cmax = (p0 + nb - 1) >> 1;
+    const long long rows = cmax - cmin + 1;
+    const int L = 2 * (int)m;
+    // the fused forms (one pass, Y written once), where the size has one
+    if (L <= 8 && !pfb2_two_pass()) {
+        if (M == 256 || M == 512) {   // about 1024 workgroups on long calls
+            const long long S = rows_run8(rows, lqrt_grid(1024, 1024), true);
+            return {M == 256 ? LQK_PFB2_AN256 : LQK_PFB2_AN512, 2 * S, cdiv(rows, S), 1};
+        }
+        if (M == 2048) {              // one workgroup per CU: about 256 runs
+            const long long S = rows_run8(rows, lqrt_grid(256, 256), true);
+            return {LQK_PFB2_AN2048, 2 * S, cdiv(rows, S), 1};
+        }
+        if (M == 4096) {              // about 256 runs (each warms up on the 2m rows before it)
+            long long S = cdiv(rows, lqrt_grid(256, 256));
+            if (S < 32) S = 32;
+            return {LQK_PFB2_AN4096, 2 * S, cdiv(rows, S), 1};
+        }
+        if (M == 64 || M == 128) {
+            // runs of S rows per set: about 2048 sets on long calls (no short
+            // extra run here: every set of a workgroup runs the same number
+            // of groups, so an extra workgroup costs a whole run -- measured
+            // 0.83 -> 1.07 ms at M = 64, r05zo)
+            const long long S = rows_run8(rows, lqrt_grid(2048, 2048), false);
+            return {LQK_PFB2_AN_SMALL, 2 * S, cdiv(cdiv(rows, S), 256 / M), 1};
+        }
+    }
+    // polyphase pass, then the batched transform: runs of S rows, >= 2048
+    // workgroups when the call is long, and runs of at least 4L rows so the
+    // L-1 warm-up rows stay a small overhead
+    const long long nsl = M / 256 ? M / 256 : 1;
+    long long S = cdiv(rows * nsl, lqrt_grid(2048, 2048));
+    if (S < 4 * L) S = 4 * L;
+    return {LQK_PFB2_POLY_FFT, 2 * S, cdiv(rows, S) * nsl, 1};
+}
+
+bool pfb2_an_chunked(unsigned M, unsigned m) { return M >= 64 && is_pow2(M) && 2 * m <= 16 && m >= 1; }
+
+// the first chunk's launch and the number of chunks (an even number of blocks
+// whose outputs fit 1 GiB: 32-bit buffer offsets)
+lqk_pfb_plan pfb2_an_plan(unsigned M, unsigned m, long long nb, int p0, long long *CB)
+{
+    lqk_pfb_plan pl = {LQK_PFB_NONE, 0, 0, 1};
+    if (M < 2 || M % 2 || m < 1 || nb < 1) return pl;
+    if (pfb2_an_chunked(M, m)) {
+        *CB = lqrt_pfb_chunk((1ll << 27) / M);
+        pl = pfb2_an_chunk(M, m, nb < *CB ? nb : *CB, p0);
+        pl.chunks = cdiv(nb, *CB);
+        return pl;
+    }
+    if (pfb2_direct_size(M)) {
+        const long long NB = M >= 1024 ? 1 : 1024 / M;
+        return {LQK_PFB2_DIRECT, NB, cdiv(nb, NB), 1};
+    }
+    if ((size_t)M * sizeof(float2) > 64 * 1024) return pl;
+    return {LQK_PFB2_GENERIC, 1, nb, 1};
+}
+
+lqk_pfb_plan pfb2_syn_plan(unsigned M, unsigned m, long long nb)
+{
+    const lqk_pfb_plan none = {LQK_PFB_NONE, 0, 0, 1};
+    if (M < 2 || M % 2 || m < 1 || nb < 1) return none;
+    if (!pfb2_two_pass() && M == 4096 && m <= 4 && nb >= 4 * (long long)m - 1 && nb * 4096ll * 8 < (1ll << 31)) {
+        long long S = cdiv(nb, lqrt_grid(256, 256));   // about 256 runs (one workgroup per CU), whole groups of three
+        S = (S + 2) / 3 * 3;
+        if (S < 33) S = 33;
+        return {LQK_PFB2_SYN4096, S, cdiv(nb, S), 1};
+    }
+    if (!pfb2_two_pass() && (M == 256 || M == 512) && m <= 4 && nb >= 16 && nb * (long long)M < (1ll << 31)) {
+        long long S = cdiv(cdiv(nb, lqrt_grid(1024, 1024)), 16) * 16;
+        if (S < 64) S = 64;
+        return {LQK_PFB2_SYN_FUSED, S, cdiv(nb, S), 1};
+    }
+    // batched transform, then the output filter: a lane per column and run of RUN blocks where 2m has a ring
+    if (2 * m == 4 || 2 * m == 6 || 2 * m == 8)
+        return {LQK_PFB2_TWO_PASS_RUN, RUN, cdiv((long long)(M / 2) * cdiv(nb, RUN), 256), 1};
+    return {LQK_PFB2_TWO_PASS_ELEM, 1, cdiv(nb * (M / 2), 256), 1};
+}
+
+const char *const ROUTE_NAMES[LQK_PFB_NROUTES] = {
+    "pfb2_an1024", "pfb2_an1024_unpaired", "pfb2_an1024_few", "pfb2_an1024_few_signal", "pfb2_an256", "pfb2_an512",
+    "pfb2_an2048", "pfb2_an4096", "pfb2_an_small", "pfb2_poly+fft", "pfb2_direct", "pfb2_generic", "pfb2_syn1024",
+    "pfb2_syn_fused", "pfb2_syn4096", "pfb2_two_pass_run", "pfb2_two_pass_elem",
+    "pfb_an1024", "pfb_an1024_unpaired", "pfb_an1024_few", "pfb_an1024_few_signal", "pfb_an_fused", "pfb_an_fused_c",
+    "pfb_an4096", "pfb_an4096_c", "pfb_an_small", "pfb_an_small_c", "pfb_an_run+fft", "pfb_an_run+fft_c",
+    "pfb_an_elem+fft", "pfb_an_elem+fft_c", "pfb_syn1024", "pfb_syn_fused", "pfb_syn_fused_c", "pfb_syn4096",
+    "pfb_syn4096_c", "pfb_syn_small", "pfb_syn_small_c", "pfb_fft+syn_run", "pfb_fft+syn_run_c", "pfb_fft+syn_elem",
+    "pfb_fft+syn_elem_c"};
+
 } // namespace
+
+extern "C" const char *lqk_pfb_route_name(int route)
+{
+    return route >= 0 && route < LQK_PFB_NROUTES ? ROUTE_NAMES[route] : nullptr;
+}
+
+extern "C" lqk_pfb_plan lqk_firpfbch2_plan(int analyzer, unsigned int M, unsigned int m, unsigned long long nblocks,
+                                           int p0, int x16, int y16, int signal)
+{
+    const lqk_pfb_plan none = {LQK_PFB_NONE, 0, 0, 1};
+    if (nblocks == 0 || nblocks > (1ull << 40) || M > (1u << 20) || m > (1u << 10)) return none;
+    lqk_pfb_plan pl = lqk_pfb2_fast_plan(analyzer, M, m, nblocks, p0, x16, y16, signal);
+    if (pl.route != LQK_PFB_NONE) return pl;
+    // (a signalling call the few-block kernel does not take goes on as a device call)
+    if (analyzer && signal) pl = lqk_pfb2_fast_plan(1, M, m, nblocks, p0, x16, y16, 0);
+    if (pl.route != LQK_PFB_NONE) return pl;
+    long long CB = 0;
+    return analyzer ? pfb2_an_plan(M, m, (long long)nblocks, p0 & 1, &CB) : pfb2_syn_plan(M, m, (long long)nblocks);
+}
 
 extern "C" void lqk_firpfbch2_analyzer(unsigned int M, unsigned int m, const void *hsub, const void *hist,
                                        const void *x, unsigned long long nblocks, int p0, void *Y, void *stream)
@@ -1269,56 +1319,57 @@ extern "C" void lqk_firpfbch2_analyzer(unsigned int M, unsigned int m, const voi
     if (nblocks == 0) return;
     hipStream_t st = (hipStream_t)stream;
     const long long nb = (long long)nblocks;
-    if (M >= 64 && is_pow2(M) && 2 * m <= 16 && m >= 1) {
-        // polyphase pass into Y, then the batched inverse transform in place
-        // (each transform kernel reads its whole block before writing it).
-        // Calls run in chunks of an even number of blocks whose outputs fit
-        // 1 GiB (32-bit buffer offsets); a later chunk's history is the
-        // input just before it (a chunk spans far more than 2mM samples).
-        const long long CB = (1ll << 27) / M;
+    long long CB = 0;
+    const lqk_pfb_plan whole = pfb2_an_plan(M, m, nb, p0, &CB);
+    if (pfb2_an_chunked(M, m)) {
+        // Calls run in chunks of an even number of blocks; a later chunk's
+        // history is the input just before it (a chunk spans far more than
+        // 2mM samples).  The polyphase pass goes into Y, then the batched
+        // inverse transform in place (each transform kernel reads its whole
+        // block before writing it).
         const long long M2 = M / 2, HL = 2ll * m * M - M2;
         for (long long b0 = 0; b0 < nb; b0 += CB) {
             const long long nbc = (nb - b0) < CB ? (nb - b0) : CB;
             const float2 *xc = (const float2 *)x + b0 * M2;
             const void *hc = b0 == 0 ? hist : (const void *)(xc - HL);
             float2 *Yc = (float2 *)Y + b0 * M;
-            // the fused forms (one pass, Y written once), where the size has one and it takes the chunk
-            bool f = false;
-            if (2 * m <= 8 && !pfb2_two_pass())
-                lq_switch<2, 4, 6, 8>(2 * m, [&](auto L) {
-                    if (M == 256 || M == 512)
-                        lq_switch<256, 512>(M, [&](auto MM) {
-                            f = launch_pfb2_an256<L, MM / 256>(hsub, hc, xc, nbc, p0, Yc, st);
-                        });
-                    else if (M == 2048)
-                        f = launch_pfb2_an2048<L>(hsub, hc, xc, nbc, p0, Yc, st);
-                    else if (M == 4096)
-                        f = launch_pfb2_an4096<L>(hsub, hc, xc, nbc, p0, Yc, st);
-                    else if (M == 64 || M == 128)
-                        lq_switch<64, 128>(M, [&](auto MM) {
-                            f = launch_pfb2_an_small<L, MM>(hsub, hc, xc, nbc, p0, Yc, st);
-                        });
-                });
-            if (f) continue;
-            bool ok = false;
-            lq_switch<2, 4, 6, 8, 10, 12, 14, 16>(
-                2 * m, [&](auto L) { ok = launch_pfb2_poly<L>((int)M, hsub, hc, xc, nbc, p0, Yc, st); });
-            if (!ok) {
+            const lqk_pfb_plan pl = pfb2_an_chunk(M, m, nbc, p0);
+            const long long S = pl.run / 2, nwg = pl.workgroups;
+            if (pl.route == LQK_PFB_NONE) {
                 fprintf(stderr, "error: firpfbch2: polyphase pass rejected a %lld-block chunk\n", nbc);
                 exit(1);
             }
-            lq_fft_batch_scaled(M, -1, Yc, Yc, nbc, 1.0f / (float)M, 1.0f, 1, 0, st);
+            if (pl.route == LQK_PFB2_POLY_FFT) {
+                lq_switch<2, 4, 6, 8, 10, 12, 14, 16>(
+                    2 * m, [&](auto L) { launch_pfb2_poly<L>((int)M, hsub, hc, xc, nbc, p0, Yc, S, nwg, st); });
+                lq_fft_batch_scaled(M, -1, Yc, Yc, nbc, 1.0f / (float)M, 1.0f, 1, 0, st);
+                continue;
+            }
+            lq_switch<2, 4, 6, 8>(2 * m, [&](auto L) {
+                switch (pl.route) {
+                case LQK_PFB2_AN256: launch_pfb2_an256<L, 1>(hsub, hc, xc, nbc, p0, Yc, S, nwg, st); break;
+                case LQK_PFB2_AN512: launch_pfb2_an256<L, 2>(hsub, hc, xc, nbc, p0, Yc, S, nwg, st); break;
+                case LQK_PFB2_AN2048: launch_pfb2_an2048<L>(hsub, hc, xc, nbc, p0, Yc, S, nwg, st); break;
+                case LQK_PFB2_AN4096: launch_pfb2_an4096<L>(hsub, hc, xc, nbc, p0, Yc, S, nwg, st); break;
+                default:
+                    lq_switch<64, 128>(M, [&](auto MM) {
+                        launch_pfb2_an_small<L, MM>(hsub, hc, xc, nbc, p0, Yc, S, nwg, st);
+                    });
+                }
+            });
         }
         return;
     }
-    if (lq_switch<2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096>(
-            M, [&](auto MM) { launch_pfb2_an<MM>(m, hsub, hist, x, nb, p0, Y, st); }))
+    if (whole.route == LQK_PFB2_DIRECT) {
+        lq_switch<2, 4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048, 4096>(
+            M, [&](auto MM) { launch_pfb2_an<MM>(m, hsub, hist, x, nb, p0, Y, whole.workgroups, st); });
         return;
-    const size_t lds = (size_t)M * sizeof(float2);
-    if (lds > 64 * 1024) {
+    }
+    if (whole.route != LQK_PFB2_GENERIC) {
         fprintf(stderr, "error: firpfbch2: %u channels not supported on the GPU path\n", M);
         exit(1);
     }
+    const size_t lds = (size_t)M * sizeof(float2);
     hipLaunchKernelGGL(k_pfb2_an_generic, dim3((unsigned)nb), dim3(NT), lds, st, (int)M, (int)m,
                        (const float *)hsub, (const float2 *)hist, (const float2 *)x, nb, p0, (float2 *)Y);
     LQ_CHECK_LAUNCH();
@@ -1332,31 +1383,39 @@ extern "C" void lqk_firpfbch2_synthesizer(unsigned int M, unsigned int m, const 
     if (nblocks == 0) return;
     if (lqk_firpfbch2_synthesizer_fast(M, m, hsub, state, X, nblocks, p0, Y, stream)) return;
     hipStream_t st = (hipStream_t)stream;
-    const long long HB = 4 * (long long)m - 1;
+    const long long HB = 4 * (long long)m - 1, nb = (long long)nblocks;
     float2 *Z = (float2 *)zscratch;
-    if (!pfb2_two_pass() && M == 4096 &&
-        launch_pfb2_syn4096((int)m, hsub, state, X, (long long)nblocks, p0, Y, Z, st)) {
-        LQ_CHECK(hipMemcpyAsync(state, Z, HB * M * sizeof(float2), hipMemcpyDeviceToDevice, st));
-        return;
-    }
-    if (!pfb2_two_pass() &&
-        launch_pfb2_syn_fused((int)M, (int)m, hsub, state, X, (long long)nblocks, p0, Y, Z, st)) {
+    const lqk_pfb_plan pl = pfb2_syn_plan(M, m, nb);
+    const unsigned grid = (unsigned)pl.workgroups;
+    if (pl.route == LQK_PFB2_SYN4096 || pl.route == LQK_PFB2_SYN_FUSED) {
+        // fused: the last 4m-1 transforms land in the scratch, then become the state
+        lq_switch<2, 4, 6, 8>(2 * m, [&](auto L) {
+            if (pl.route == LQK_PFB2_SYN4096)
+                hipLaunchKernelGGL((k_pfb2_syn4096<L>), dim3(grid), dim3(1024), 0, st, (const float *)hsub,
+                                   (const float2 *)state, (const float2 *)X, (int)nb, p0, (int)pl.run, (float2 *)Y,
+                                   (float2 *)Z, (const float2 *)lqrt_twiddles());
+            else
+                lq_switch<256, 512>(M, [&](auto MM) {
+                    hipLaunchKernelGGL((k_pfb2_syn_fused<L, MM / 256>), dim3(grid), dim3(MM), 0, st,
+                                       (const float *)hsub, (const float2 *)state, (const float2 *)X, (int)nb, p0,
+                                       (int)pl.run, (float2 *)Y, (float2 *)Z, (const float2 *)lqrt_twiddles());
+                });
+        });
+        LQ_CHECK_LAUNCH();
         LQ_CHECK(hipMemcpyAsync(state, Z, HB * M * sizeof(float2), hipMemcpyDeviceToDevice, st));
         return;
     }
     LQ_CHECK(hipMemcpyAsync(Z, state, HB * M * sizeof(float2), hipMemcpyDeviceToDevice, st));
-    lq_fft_batch_scaled(M, -1, X, Z + HB * M, (long long)nblocks, 1.0f / (float)M, (float)(M / 2), 1, 1, st);
-    const long long tot = (long long)nblocks * (M / 2);
-    const long long runs = (long long)(M / 2) * (((long long)nblocks + RUN - 1) / RUN);
-    const dim3 gr((unsigned)((runs + 255) / 256));
-    if (!lq_switch<4, 6, 8>(2 * m, [&](auto L) {
-            hipLaunchKernelGGL(k_pfb2_syn_out_run<L>, gr, dim3(256), 0, st, (int)M, (const float *)hsub,
-                               (const float2 *)Z, (long long)nblocks, p0, (float2 *)Y);
-        }))
-        hipLaunchKernelGGL(k_pfb2_syn_out, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, (int)M, (int)m,
-                           (const float *)hsub, (const float2 *)Z, (long long)nblocks, p0, (float2 *)Y);
+    lq_fft_batch_scaled(M, -1, X, Z + HB * M, nb, 1.0f / (float)M, (float)(M / 2), 1, 1, st);
+    if (pl.route == LQK_PFB2_TWO_PASS_RUN)
+        lq_switch<4, 6, 8>(2 * m, [&](auto L) {
+            hipLaunchKernelGGL(k_pfb2_syn_out_run<L>, dim3(grid), dim3(256), 0, st, (int)M, (const float *)hsub,
+                               (const float2 *)Z, nb, p0, (float2 *)Y);
+        });
+    else
+        hipLaunchKernelGGL(k_pfb2_syn_out, dim3(grid), dim3(256), 0, st, (int)M, (int)m, (const float *)hsub,
+                           (const float2 *)Z, nb, p0, (float2 *)Y);
     LQ_CHECK_LAUNCH();
     // keep the newest HB z vectors as the state for the next call
-    LQ_CHECK(hipMemcpyAsync(state, Z + (long long)nblocks * M, HB * M * sizeof(float2), hipMemcpyDeviceToDevice,
-                            st));
+    LQ_CHECK(hipMemcpyAsync(state, Z + nb * M, HB * M * sizeof(float2), hipMemcpyDeviceToDevice, st));
 }

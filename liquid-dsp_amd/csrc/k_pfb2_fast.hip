@@ -792,7 +792,78 @@ __global__ __launch_bounds__(NT, 1) void k_pfb2_syn1024(const float2 *__restrict
     }
 }
 
+// ------------------------------------------------------------------ what a launch decides
+// Groups of 16 blocks per workgroup: about one workgroup per CU (the target,
+// which liquid_mi355x_set_max_workgroups lowers), each at least `least'.
+struct Groups {
+    long long gpw, nwg;
+};
+Groups pfb_groups(long long ngroups, long long least)
+{
+    const long long T = lqrt_grid(256, 256);
+    long long gpw = (ngroups + T - 1) / T;
+    if (gpw < least) gpw = least;
+    return {gpw, (ngroups + gpw - 1) / gpw};
+}
+
+// one launch of k_pfb2_an1024: nb blocks from absolute block B0
+lqk_pfb_plan pfb2_an1024_chunk(long long nb, long long B0, bool pair)
+{
+    const long long ngroups = (B0 + nb - 1) / 16 - B0 / 16 + 1;   // 16-block groups the blocks touch
+    // one workgroup per CU (LDS-bound), each at least 4 groups (64 blocks)
+    const Groups g = pfb_groups(ngroups, 4);
+    return {pair ? LQK_PFB2_AN1024 : LQK_PFB2_AN1024_UNPAIRED, 16 * g.gpw, g.nwg, 1};
+}
+
+// one launch of k_pfb_an1024: nb blocks
+lqk_pfb_plan pfb_an1024_chunk(long long nb, bool pair)
+{
+    const Groups g = pfb_groups((nb + 15) / 16, 2);
+    return {pair ? LQK_PFB_AN1024 : LQK_PFB_AN1024_UNPAIRED, 16 * g.gpw, g.nwg, 1};
+}
+
+constexpr long long PFB2_CH = 1LL << 18, PFB_CH = 1LL << 17;   // blocks per launch: 2^27 samples
+
 } // namespace
+
+extern "C" lqk_pfb_plan lqk_pfb2_fast_plan(int analyzer, unsigned int Mch, unsigned int m, unsigned long long nblocks,
+                                           int p0, int x16, int y16, int signal)
+{
+    lqk_pfb_plan pl = {LQK_PFB_NONE, 0, 0, 1};
+    if (Mch != (unsigned)M || !(m == 4 || m == 2) || nblocks == 0) return pl;
+    if (!analyzer) {
+        if (nblocks < 4 * m - 1) return pl;
+        const Groups g = pfb_groups(((long long)nblocks + 15) / 16, 2);
+        return {LQK_PFB2_SYN1024, 16 * g.gpw, g.nwg, 1};
+    }
+    if (!y16) return pl;   // Y: 16-byte (two-bin) non-temporal stores
+    if (nblocks <= 16)     // a few blocks: one workgroup, no warm-up rows
+        return {signal ? LQK_PFB2_AN1024_FEW_SIGNAL : LQK_PFB2_AN1024_FEW, 16, 1, 1};
+    if (signal) return pl;   // (the signalling form is the few-block kernel's)
+    const long long CH = lqrt_pfb_chunk(PFB2_CH);
+    pl = pfb2_an1024_chunk((long long)nblocks < CH ? (long long)nblocks : CH, p0 & 1, x16 != 0);
+    pl.chunks = ((long long)nblocks + CH - 1) / CH;
+    return pl;
+}
+
+extern "C" lqk_pfb_plan lqk_pfb_fast_plan(int analyzer, int ctaps, unsigned int Mch, unsigned int p,
+                                          unsigned long long nblocks, int x16, int y16, int signal)
+{
+    lqk_pfb_plan pl = {LQK_PFB_NONE, 0, 0, 1};
+    if (ctaps || Mch != (unsigned)M || !(p == 8 || p == 4) || nblocks == 0) return pl;
+    if (!analyzer) {
+        if (nblocks < p - 1) return pl;
+        const Groups g = pfb_groups(((long long)nblocks + 15) / 16, 2);
+        return {LQK_PFB_SYN1024, 16 * g.gpw, g.nwg, 1};
+    }
+    if (!y16) return pl;
+    if (nblocks <= 16) return {signal ? LQK_PFB_AN1024_FEW_SIGNAL : LQK_PFB_AN1024_FEW, 16, 1, 1};
+    if (signal) return pl;
+    const long long CH = lqrt_pfb_chunk(PFB_CH);
+    pl = pfb_an1024_chunk((long long)nblocks < CH ? (long long)nblocks : CH, x16 != 0);
+    pl.chunks = ((long long)nblocks + CH - 1) / CH;
+    return pl;
+}
 
 // Returns 1 if handled by the fast path.  Launches cover at most 2^18 blocks
 // (2^27 input samples) so every buffer offset fits 31 bits; later chunks take
@@ -801,13 +872,17 @@ extern "C" int lqk_firpfbch2_analyzer_fast(unsigned int Mch, unsigned int m, con
                                            const void *x, unsigned long long nblocks, long long B0, void *Y,
                                            const lqk_hist_job *job, unsigned *flag, unsigned seq, void *stream)
 {
-    if (Mch != (unsigned)M || !(m == 4 || m == 2)) return 0;
     // x / hist: 8-byte sample loads; Y: 16-byte (two-bin) non-temporal stores
-    if (((uintptr_t)x & 7) || ((uintptr_t)hist & 7) || ((uintptr_t)Y & 15)) return 0;
+    if (((uintptr_t)x & 7) || ((uintptr_t)hist & 7)) return 0;
+    const long long HL = 2LL * m * M - M2;
+    const bool pair0 = ((uintptr_t)x & 15) == 0 && ((uintptr_t)((const float2 *)hist + HL) & 15) == 0;
+    const lqk_pfb_plan whole = lqk_pfb2_fast_plan(1, Mch, m, nblocks ? nblocks : 1, (int)(B0 & 1), pair0,
+                                                  ((uintptr_t)Y & 15) == 0, flag != nullptr);
+    if (whole.route == LQK_PFB_NONE) return 0;
     if (nblocks == 0) return 1;
     hipStream_t st = (hipStream_t)stream;
     const float2 *tw = (const float2 *)lqrt_twiddles();
-    if (nblocks <= 16) {   // a few blocks: one workgroup, no warm-up rows
+    if (whole.route == LQK_PFB2_AN1024_FEW || whole.route == LQK_PFB2_AN1024_FEW_SIGNAL) {
         const lqk_hist_job hj = job ? *job : lqk_hist_job{nullptr, nullptr, 0ull, nullptr, 0u};
         const int p0 = (int)(B0 & 1);
         lq_switch<4, 8>(2 * m, [&](auto L) {
@@ -818,9 +893,7 @@ extern "C" int lqk_firpfbch2_analyzer_fast(unsigned int Mch, unsigned int m, con
         LQ_CHECK_LAUNCH();
         return 1;
     }
-    const long long HL = 2LL * m * M - M2;
-    const long long CH = 1LL << 18;
-    if (flag) return 0;   // (the signalling form is the few-block kernel's)
+    const long long CH = lqrt_pfb_chunk(PFB2_CH);
     for (long long ob = 0; ob < (long long)nblocks; ob += CH) {
         const long long nb = ((long long)nblocks - ob) < CH ? ((long long)nblocks - ob) : CH;
         Params P;
@@ -833,18 +906,13 @@ extern "C" int lqk_firpfbch2_analyzer_fast(unsigned int Mch, unsigned int m, con
         P.zero = (const float2 *)lqrt_zeros();
         P.hj = {nullptr, nullptr, 0ull, nullptr, 0u};
         if (ob == 0 && job) P.hj = *job;
-        const long long gfirst = P.B0 / 16;                // 16-block group containing the first block
-        const long long glast = (P.B0 + nb - 1) / 16;      // inclusive
-        const long long ngroups = glast - gfirst + 1;
-        // one workgroup per CU (LDS-bound), each at least 4 groups (64 blocks)
-        long long gpw = (ngroups + 255) / 256;
-        if (gpw < 4) gpw = 4;
-        const long long nwg = (ngroups + gpw - 1) / gpw;
-        P.gs0 = gfirst;
-        P.gpw = (int)gpw;
-        P.gend = glast + 1;
         // paired 16-byte row loads need x and the history 16-byte aligned
         const bool pair = ((uintptr_t)P.x & 15) == 0 && ((uintptr_t)(P.hist + HL) & 15) == 0;
+        const lqk_pfb_plan pl = pfb2_an1024_chunk(nb, P.B0, pair);
+        const long long nwg = pl.workgroups;
+        P.gs0 = P.B0 / 16;                       // 16-block group containing the first block
+        P.gpw = (int)(pl.run / 16);
+        P.gend = (P.B0 + nb - 1) / 16 + 1;       // past the group of the last block
         lq_switch<4, 8>(2 * m, [&](auto L) {
             lq_switch<1, 0>(pair, [&](auto pr) {
                 hipLaunchKernelGGL((k_pfb2_an1024<L, pr != 0>), dim3((unsigned)nwg), dim3(NT), 0, st, P,
@@ -863,23 +931,24 @@ extern "C" int lqk_firpfbch_analyzer_fast(int ctaps, unsigned int Mch, unsigned 
                                           const void *hist, const void *x, unsigned long long nblocks, void *Y,
                                           void *stream)
 {
-    if (ctaps || Mch != (unsigned)M || !(p == 8 || p == 4)) return 0;
-    if (((uintptr_t)x & 7) || ((uintptr_t)hist & 7) || ((uintptr_t)Y & 15)) return 0;
+    if (((uintptr_t)x & 7) || ((uintptr_t)hist & 7)) return 0;
+    // (calls of at most 16 blocks reach lqk_firpfbch_analyzer_few first; here they run as any other)
+    if (lqk_pfb_fast_plan(1, ctaps, Mch, p, nblocks ? nblocks : 1, 1, ((uintptr_t)Y & 15) == 0, 0).route == LQK_PFB_NONE)
+        return 0;
     if (nblocks == 0) return 1;
     hipStream_t st = (hipStream_t)stream;
     const float2 *tw = (const float2 *)lqrt_twiddles();
     const long long HL = (long long)(p - 1) * M;
-    const long long CH = 1LL << 17;
+    const long long CH = lqrt_pfb_chunk(PFB_CH);
     for (long long ob = 0; ob < (long long)nblocks; ob += CH) {
         const long long nb = ((long long)nblocks - ob) < CH ? ((long long)nblocks - ob) : CH;
         const float2 *xs = (const float2 *)x + ob * M;
         const float2 *hs = ob == 0 ? (const float2 *)hist : xs - HL;
-        const long long ngroups = (nb + 15) / 16;
-        long long gpw = (ngroups + 255) / 256;
-        if (gpw < 2) gpw = 2;
-        const unsigned nwg = (unsigned)((ngroups + gpw - 1) / gpw);
         const float2 *zero = (const float2 *)lqrt_zeros();
         const bool pair = ((uintptr_t)xs & 15) == 0 && ((uintptr_t)hs & 15) == 0;
+        const lqk_pfb_plan pl = pfb_an1024_chunk(nb, pair);
+        const unsigned nwg = (unsigned)pl.workgroups;
+        const long long gpw = pl.run / 16;
         lq_switch<4, 8>(p, [&](auto PP) {   // PF = 16 rows in flight at P = 4, 8 at P = 8
             lq_switch<1, 0>(pair, [&](auto pr) {
                 hipLaunchKernelGGL((k_pfb_an1024<PP, PP == 8 ? 8 : 16, pr != 0>), dim3(nwg), dim3(NT), 0, st, hs, xs,
@@ -899,8 +968,9 @@ extern "C" int lqk_firpfbch_analyzer_few(int ctaps, unsigned int Mch, unsigned i
                                          const void *hist, const void *x, unsigned long long nblocks, void *Y,
                                          const lqk_hist_job *job, unsigned *flag, unsigned seq, void *stream)
 {
-    if (ctaps || Mch != (unsigned)M || !(p == 8 || p == 4) || nblocks == 0 || nblocks > 16) return 0;
-    if (((uintptr_t)x & 7) || ((uintptr_t)hist & 7) || ((uintptr_t)Y & 15)) return 0;
+    if (((uintptr_t)x & 7) || ((uintptr_t)hist & 7)) return 0;
+    const int route = lqk_pfb_fast_plan(1, ctaps, Mch, p, nblocks, 1, ((uintptr_t)Y & 15) == 0, flag != nullptr).route;
+    if (route != LQK_PFB_AN1024_FEW && route != LQK_PFB_AN1024_FEW_SIGNAL) return 0;
     hipStream_t st = (hipStream_t)stream;
     const float2 *tw = (const float2 *)lqrt_twiddles();
     const lqk_hist_job hj = job ? *job : lqk_hist_job{nullptr, nullptr, 0ull, nullptr, 0u};
@@ -918,14 +988,13 @@ extern "C" int lqk_firpfbch_synthesizer_fast(int ctaps, unsigned int Mch, unsign
                                              void *state, const void *X, unsigned long long nblocks, void *y,
                                              void *stream)
 {
-    if (ctaps || Mch != (unsigned)M || !(p == 8 || p == 4) || nblocks < p - 1) return 0;
+    const lqk_pfb_plan pl = lqk_pfb_fast_plan(0, ctaps, Mch, p, nblocks, 1, 1, 0);
+    if (pl.route != LQK_PFB_SYN1024) return 0;
     if (((uintptr_t)X & 7) || ((uintptr_t)y & 7)) return 0;
     hipStream_t st = (hipStream_t)stream;
     const float2 *tw = (const float2 *)lqrt_twiddles();
-    const long long ngroups = ((long long)nblocks + 15) / 16;
-    long long gpw = (ngroups + 255) / 256;
-    if (gpw < 2) gpw = 2;
-    const unsigned nwg = (unsigned)((ngroups + gpw - 1) / gpw);
+    const unsigned nwg = (unsigned)pl.workgroups;
+    const long long gpw = pl.run / 16;
     lq_switch<4, 8>(p, [&](auto PP) {
         hipLaunchKernelGGL((k_pfb_syn1024<PP>), dim3(nwg), dim3(NT), 0, st, (const float2 *)X, (long long)nblocks,
                            (int)gpw, (const float *)hsub, (const float2 *)state, tw, (float2 *)y);
@@ -943,14 +1012,13 @@ extern "C" int lqk_firpfbch2_synthesizer_fast(unsigned int Mch, unsigned int m, 
                                               void *stream)
 {
     const unsigned HB = 4 * m - 1;
-    if (Mch != (unsigned)M || !(m == 4 || m == 2) || nblocks < HB) return 0;
+    const lqk_pfb_plan pl = lqk_pfb2_fast_plan(0, Mch, m, nblocks, p0, 1, 1, 0);
+    if (pl.route != LQK_PFB2_SYN1024) return 0;
     if (((uintptr_t)X & 7) || ((uintptr_t)Y & 7)) return 0;
     hipStream_t st = (hipStream_t)stream;
     const float2 *tw = (const float2 *)lqrt_twiddles();
-    const long long ngroups = ((long long)nblocks + 15) / 16;
-    long long gpw = (ngroups + 255) / 256;
-    if (gpw < 2) gpw = 2;
-    const unsigned nwg = (unsigned)((ngroups + gpw - 1) / gpw);
+    const unsigned nwg = (unsigned)pl.workgroups;
+    const long long gpw = pl.run / 16;
     lq_switch<4, 8>(2 * m, [&](auto L) {
         hipLaunchKernelGGL((k_pfb2_syn1024<L>), dim3(nwg), dim3(NT), 0, st, (const float2 *)X, (long long)nblocks,
                            p0 & 1, (int)gpw, (const float *)hsub, (const float2 *)state, tw, (float2 *)Y);

@@ -207,6 +207,85 @@ void lqk_firpfbch_synthesizer(int ctaps, unsigned int M, unsigned int p, const v
                               void *zscratch, const void *X, unsigned long long nblocks, void *y,
                               void *stream);
 
+/* ---------------------------------------------------------------- channelizer routes
+ * What a firpfbch2 / firpfbch launch decides, formed by one host function per
+ * ladder that the launch itself calls (k_firpfbch2.hip, k_firpfbch.hip,
+ * k_pfb2_fast.hip), so a query cannot drift from the launch.  A route is one
+ * kernel template family plus what a test must tell apart (paired or 8-byte
+ * loads, the few-block and the signalling form, real or complex taps `_c');
+ * the unrolled depth (L, P) and the size within a family are not part of it.
+ * Every hipLaunchKernelGGL of the three files belongs to exactly one route
+ * (DESIGN.md has the table). */
+enum {
+    LQK_PFB_NONE = -1,                 /* not handled here / impossible arguments */
+    LQK_PFB2_AN1024 = 0,               /* k_pfb2_an1024<L, true> */
+    LQK_PFB2_AN1024_UNPAIRED,          /* k_pfb2_an1024<L, false> */
+    LQK_PFB2_AN1024_FEW,               /* k_pfb2_an1024_few<L> */
+    LQK_PFB2_AN1024_FEW_SIGNAL,        /* the same kernel raising the host's completion flag */
+    LQK_PFB2_AN256,                    /* k_pfb2_an256<L, 1> */
+    LQK_PFB2_AN512,                    /* k_pfb2_an256<L, 2> */
+    LQK_PFB2_AN2048,                   /* k_pfb2_an2048<L> */
+    LQK_PFB2_AN4096,                   /* k_pfb2_an4096<L> */
+    LQK_PFB2_AN_SMALL,                 /* k_pfb2_an_small<L, 64 | 128> */
+    LQK_PFB2_POLY_FFT,                 /* k_pfb2_poly<L> + batched transform */
+    LQK_PFB2_DIRECT,                   /* k_pfb2_an<M, NB> */
+    LQK_PFB2_GENERIC,                  /* k_pfb2_an_generic */
+    LQK_PFB2_SYN1024,                  /* k_pfb2_syn1024<L> + state transform */
+    LQK_PFB2_SYN_FUSED,                /* k_pfb2_syn_fused<L, 1 | 2> */
+    LQK_PFB2_SYN4096,                  /* k_pfb2_syn4096<L> */
+    LQK_PFB2_TWO_PASS_RUN,             /* batched transform + k_pfb2_syn_out_run<L> */
+    LQK_PFB2_TWO_PASS_ELEM,            /* batched transform + k_pfb2_syn_out */
+    LQK_PFB_AN1024,                    /* k_pfb_an1024<P, PF, true> */
+    LQK_PFB_AN1024_UNPAIRED,           /* k_pfb_an1024<P, PF, false> */
+    LQK_PFB_AN1024_FEW,                /* k_pfb_an1024_few<P> */
+    LQK_PFB_AN1024_FEW_SIGNAL,
+    LQK_PFB_AN_FUSED,                  /* k_pfb_an_fused<P, float, 1 | 2> */
+    LQK_PFB_AN_FUSED_C,                /* ... <P, float2, R>; the `_C' routes follow their real one by 1 */
+    LQK_PFB_AN4096,
+    LQK_PFB_AN4096_C,
+    LQK_PFB_AN_SMALL,
+    LQK_PFB_AN_SMALL_C,
+    LQK_PFB_AN_RUN_FFT,                /* k_pfb_an_X_run<P, TC> + batched transform */
+    LQK_PFB_AN_RUN_FFT_C,
+    LQK_PFB_AN_ELEM_FFT,               /* k_pfb_an_X<TC> + batched transform */
+    LQK_PFB_AN_ELEM_FFT_C,
+    LQK_PFB_SYN1024,                   /* k_pfb_syn1024<P> + state transform */
+    LQK_PFB_SYN_FUSED,
+    LQK_PFB_SYN_FUSED_C,
+    LQK_PFB_SYN4096,
+    LQK_PFB_SYN4096_C,
+    LQK_PFB_SYN_SMALL,
+    LQK_PFB_SYN_SMALL_C,
+    LQK_PFB_FFT_SYN_RUN,               /* batched transform + k_pfb_syn_out_run<P, TC> */
+    LQK_PFB_FFT_SYN_RUN_C,
+    LQK_PFB_FFT_SYN_ELEM,              /* batched transform + k_pfb_syn_out<TC> */
+    LQK_PFB_FFT_SYN_ELEM_C,
+    LQK_PFB_NROUTES
+};
+/* run: blocks one workgroup (or one column set of it) walks, of the first
+ * chunk; workgroups: that chunk's grid (for the two-pass forms the filter
+ * kernel's); chunks: launches the call is cut into */
+typedef struct {
+    int route;
+    long long run, workgroups, chunks;
+} lqk_pfb_plan;
+/* the M = 1024 fast ladders (k_pfb2_fast.hip); route LQK_PFB_NONE: not theirs.
+ * signal: the call comes with a completion flag (a host call whose output fits
+ * LQRT_COPYOUT_MAX).  x and Y are taken as 8-byte aligned; x16 / y16: 16-byte */
+lqk_pfb_plan lqk_pfb2_fast_plan(int analyzer, unsigned int M, unsigned int m, unsigned long long nblocks, int p0,
+                                int x16, int y16, int signal);
+lqk_pfb_plan lqk_pfb_fast_plan(int analyzer, int ctaps, unsigned int M, unsigned int p, unsigned long long nblocks,
+                               int x16, int y16, int signal);
+/* the whole ladder, as the host objects walk it (fast forms first) */
+lqk_pfb_plan lqk_firpfbch2_plan(int analyzer, unsigned int M, unsigned int m, unsigned long long nblocks, int p0,
+                                int x16, int y16, int signal);
+lqk_pfb_plan lqk_firpfbch_plan(int analyzer, int ctaps, unsigned int M, unsigned int p, unsigned long long nblocks,
+                               int x16, int y16, int signal);
+const char *lqk_pfb_route_name(int route);
+/* blocks per launch of the chunking analyzers: liquid_mi355x_set_channelizer_chunk's
+ * value (tests only), or dflt when none is set */
+long long lqrt_pfb_chunk(long long dflt);
+
 /* ---------------------------------------------------------------- FFT / fftfilt */
 /* batched complex FFT of power-of-two size n (2..4096): dir +1 forward, -1 backward */
 void lqk_fft_batch(unsigned int n, int dir, const void *x, void *y, unsigned long long batch,

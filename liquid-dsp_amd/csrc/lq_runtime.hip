@@ -187,6 +187,36 @@ extern "C" unsigned lqrt_grid(unsigned long long want, unsigned cap)
     return (unsigned)g;
 }
 
+// ------------------------------------------------------- channelizer chunk
+// The chunking analyzers (lqk_firpfbch2_analyzer, lqk_firpfbch2_analyzer_fast,
+// lqk_firpfbch_analyzer_fast) cut a call into launches of 2^27 / M, 2^18 and
+// 2^17 blocks.  A nonzero value here replaces all three, so the tests reach
+// the seams between launches at sizes that take milliseconds; nothing else
+// sets it.  Refused (-1, the value unchanged): below 64 or no multiple of 32.
+// The block parity is carried per chunk (an even size), the M = 1024 kernels
+// count their groups of 16 blocks from the absolute block index, and a later
+// chunk reads its history from the input before it, which a chunk of 64
+// blocks covers twice over (the longest window is 31 blocks, at m = 8).
+static long long g_pfb_chunk = 0;
+
+extern "C" int liquid_mi355x_set_channelizer_chunk(unsigned long long blocks)
+{
+    if (blocks != 0 && (blocks < 64 || blocks % 32 != 0 || blocks > (1ull << 27))) return -1;
+    __atomic_store_n(&g_pfb_chunk, (long long)blocks, __ATOMIC_RELAXED);
+    return 0;
+}
+
+extern "C" unsigned long long liquid_mi355x_get_channelizer_chunk(void)
+{
+    return (unsigned long long)__atomic_load_n(&g_pfb_chunk, __ATOMIC_RELAXED);
+}
+
+extern "C" long long lqrt_pfb_chunk(long long dflt)
+{
+    const long long v = __atomic_load_n(&g_pfb_chunk, __ATOMIC_RELAXED);
+    return v && v < dflt ? v : dflt;   // never past the default: the kernels' offsets are 32 bits wide
+}
+
 // ------------------------------------------------------------ small calls
 // The per-call liquid.h API (firfilt_execute, dotprod_execute,
 // firpfbch2_execute ...) returns only after its result is in host memory.

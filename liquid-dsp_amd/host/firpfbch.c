@@ -177,12 +177,19 @@ static void lq_pfbch_block_dev(lq_pfbch *q, const void *dx, unsigned long long n
     }
 }
 
+/* a host call whose output fits the pinned completion buffer: the analyzer
+ * tries the signalling few-block launch first */
+static int lq_pfbch_signals(int type, unsigned int M, unsigned long long nblocks)
+{
+    return type == LIQUID_ANALYZER && nblocks * M * 8 <= LQRT_COPYOUT_MAX;
+}
+
 static void lq_pfbch_block(lq_pfbch *q, const void *x, unsigned long long nblocks, void *y)
 {
     if (nblocks == 0) return;
     size_t bytes = (size_t)nblocks * q->M * 8;
     const void *dx = lq_call_in(&q->ctx, &q->xbuf, x, bytes);
-    if (q->type == LIQUID_ANALYZER && bytes <= LQRT_COPYOUT_MAX) {
+    if (lq_pfbch_signals(q->type, q->M, nblocks)) {
         /* a few blocks (the reference's execute() is one): the kernel writes
          * the pinned output buffer and raises the completion flag itself */
         unsigned *flag, seq;
@@ -248,3 +255,21 @@ static void lq_pfbch_block(lq_pfbch *q, const void *x, unsigned long long nblock
 
 LQ_FIRPFBCH_FRONT(firpfbch_crcf, LQ_CRCF, float)
 LQ_FIRPFBCH_FRONT(firpfbch_cccf, LQ_CCCF, liquid_float_complex)
+
+/* what a call launches (liquid_mi355x.h); lqk_firpfbch_plan is the launches' own decision */
+int liquid_mi355x_firpfbch_route(int _kind, int _type, unsigned int _M, unsigned int _p, unsigned long long _nblocks,
+                                 int _x_aligned16, int _y_aligned16, int _host_call, unsigned long long *_run,
+                                 unsigned long long *_workgroups, unsigned long long *_chunks)
+{
+    if ((_kind != LQ_CRCF && _kind != LQ_CCCF) || (_type != LIQUID_ANALYZER && _type != LIQUID_SYNTHESIZER) ||
+        _M == 0 || _p == 0 || _nblocks == 0)
+        return -1;
+    const lqk_pfb_plan pl = lqk_firpfbch_plan(_type == LIQUID_ANALYZER, _kind == LQ_CCCF, _M, _p, _nblocks,
+                                              _x_aligned16, _y_aligned16,
+                                              _host_call && lq_pfbch_signals(_type, _M, _nblocks));
+    if (pl.route < 0) return -1;
+    if (_run) *_run = (unsigned long long)pl.run;
+    if (_workgroups) *_workgroups = (unsigned long long)pl.workgroups;
+    if (_chunks) *_chunks = (unsigned long long)pl.chunks;
+    return pl.route;
+}

@@ -156,6 +156,13 @@ void firpfbch2_crcf_execute_block_dev(firpfbch2_crcf _q, const liquid_float_comp
     _q->flag = (int)((_q->flag + _nblocks) & 1);
 }
 
+/* a host call whose output fits the pinned completion buffer: the analyzer
+ * tries the signalling few-block launch first */
+static int firpfbch2_signals(int type, unsigned int M, unsigned long long nblocks)
+{
+    return type == LIQUID_ANALYZER && nblocks * M * 8 <= LQRT_COPYOUT_MAX;
+}
+
 void firpfbch2_crcf_execute_block(firpfbch2_crcf _q, liquid_float_complex *_x, unsigned long long _nblocks,
                                   liquid_float_complex *_y)
 {
@@ -163,7 +170,7 @@ void firpfbch2_crcf_execute_block(firpfbch2_crcf _q, liquid_float_complex *_x, u
     size_t nin = (size_t)_nblocks * (_q->type == LIQUID_ANALYZER ? _q->M / 2 : _q->M);
     size_t nout = (size_t)_nblocks * (_q->type == LIQUID_ANALYZER ? _q->M : _q->M / 2);
     const void *dx = lq_call_in(&_q->ctx, &_q->xbuf, _x, nin * 8);
-    if (_q->type == LIQUID_ANALYZER && nout * 8 <= LQRT_COPYOUT_MAX) {
+    if (firpfbch2_signals(_q->type, _q->M, _nblocks)) {
         /* a few blocks (the reference's execute() is one): the kernel writes
          * the pinned output buffer and raises the completion flag itself --
          * one launch per call, no copy-out kernel */
@@ -188,3 +195,30 @@ void firpfbch2_crcf_execute(firpfbch2_crcf _q, liquid_float_complex *_x, liquid_
 void firpfbch2_crcf_set_stream(firpfbch2_crcf _q, void *_s) { lq_ctx_set_stream(&_q->ctx, _s); }
 void *firpfbch2_crcf_get_stream(firpfbch2_crcf _q) { return _q->ctx.stream; }
 void firpfbch2_crcf_synchronize(firpfbch2_crcf _q) { lqrt_sync(_q->ctx.stream); }
+
+/* what a call launches (liquid_mi355x.h); lqk_firpfbch2_plan is the launches' own decision */
+int liquid_mi355x_firpfbch2_route(int _type, unsigned int _M, unsigned int _m, unsigned long long _nblocks,
+                                  int _first_block_parity, int _x_aligned16, int _y_aligned16, int _host_call,
+                                  unsigned long long *_run, unsigned long long *_workgroups,
+                                  unsigned long long *_chunks)
+{
+    if ((_type != LIQUID_ANALYZER && _type != LIQUID_SYNTHESIZER) || _M < 2 || _M % 2 || _m < 1 || _nblocks == 0)
+        return -1;
+    const lqk_pfb_plan pl = lqk_firpfbch2_plan(_type == LIQUID_ANALYZER, _M, _m, _nblocks, _first_block_parity & 1,
+                                               _x_aligned16, _y_aligned16,
+                                               _host_call && firpfbch2_signals(_type, _M, _nblocks));
+    if (pl.route < 0) return -1;
+    if (_run) *_run = (unsigned long long)pl.run;
+    if (_workgroups) *_workgroups = (unsigned long long)pl.workgroups;
+    if (_chunks) *_chunks = (unsigned long long)pl.chunks;
+    return pl.route;
+}
+
+int liquid_mi355x_channelizer_route_count(void)
+{
+    int n = 0;
+    while (lqk_pfb_route_name(n)) n++;
+    return n;
+}
+
+const char *liquid_mi355x_channelizer_route_name(int _i) { return lqk_pfb_route_name(_i); }

@@ -10,6 +10,7 @@ with a message if no HIP device exists (no CPU fallback).
 When torch is imported in the same process, import it BEFORE this module so
 that the library binds torch's HIP runtime (one runtime per process).
 """
+import collections
 import ctypes as C
 import os
 import re
@@ -67,6 +68,52 @@ def set_max_workgroups(n):
 
 def get_max_workgroups():
     return int(lib().liquid_mi355x_get_max_workgroups())
+
+
+PfbRoute = collections.namedtuple("PfbRoute", "route run workgroups chunks")
+
+
+def channelizer_routes():
+    """Every route firpfbch2_route and firpfbch_route can return, by name."""
+    L = lib()
+    return tuple(L.liquid_mi355x_channelizer_route_name(k).decode()
+                 for k in range(L.liquid_mi355x_channelizer_route_count()))
+
+
+def _pfb_route(fn, args):
+    run, wg, ch = C.c_ulonglong(0), C.c_ulonglong(0), C.c_ulonglong(0)
+    r = int(fn(*args, C.byref(run), C.byref(wg), C.byref(ch)))
+    if r < 0:
+        raise ValueError("%s: bad arguments %r" % (fn.__name__, args))
+    return PfbRoute(lib().liquid_mi355x_channelizer_route_name(r).decode(), int(run.value), int(wg.value),
+                    int(ch.value))
+
+
+def firpfbch2_route(typ, M, m, nblocks, parity=0, x_aligned16=True, y_aligned16=True, host_call=False):
+    """What a firpfbch2 call of nblocks blocks launches (no GPU call): the
+    route's name, the blocks one workgroup run walks, the workgroups and the
+    launches (chunks).  liquid_mi355x_firpfbch2_route."""
+    return _pfb_route(lib().liquid_mi355x_firpfbch2_route,
+                      (int(typ), int(M), int(m), int(nblocks), int(parity) & 1, int(bool(x_aligned16)),
+                       int(bool(y_aligned16)), int(bool(host_call))))
+
+
+def firpfbch_route(t, typ, M, p, nblocks, x_aligned16=True, y_aligned16=True, host_call=False):
+    """As firpfbch2_route for firpfbch_crcf / firpfbch_cccf (t "crcf" / "cccf")."""
+    return _pfb_route(lib().liquid_mi355x_firpfbch_route,
+                      (_KINDS[t], int(typ), int(M), int(p), int(nblocks), int(bool(x_aligned16)),
+                       int(bool(y_aligned16)), int(bool(host_call))))
+
+
+def set_channelizer_chunk(blocks):
+    """Blocks per launch of the chunking channelizer analyzers (0: the
+    defaults); ValueError where the library refuses the value.  For tests."""
+    if lib().liquid_mi355x_set_channelizer_chunk(int(blocks)) != 0:
+        raise ValueError("set_channelizer_chunk: %d refused (0, or a multiple of 32 from 64 up)" % blocks)
+
+
+def get_channelizer_chunk():
+    return int(lib().liquid_mi355x_get_channelizer_chunk())
 
 
 # liquid_mi355x_firdecim_route's codes, by name
@@ -646,6 +693,12 @@ def _declare(L):
         "liquid_mi355x_device_synchronize": (None, []),
         "liquid_mi355x_set_max_workgroups": (None, [u]),
         "liquid_mi355x_get_max_workgroups": (u, []),
+        "liquid_mi355x_firpfbch2_route": (i, [i, u, u, ull, i, i, i, i, vp, vp, vp]),
+        "liquid_mi355x_firpfbch_route": (i, [i, i, u, u, ull, i, i, i, vp, vp, vp]),
+        "liquid_mi355x_channelizer_route_count": (i, []),
+        "liquid_mi355x_channelizer_route_name": (C.c_char_p, [i]),
+        "liquid_mi355x_set_channelizer_chunk": (i, [ull]),
+        "liquid_mi355x_get_channelizer_chunk": (ull, []),
         "liquid_mi355x_pinned_input_max": (u, []),
         "liquid_mi355x_copyout_max": (u, []),
         "liquid_mi355x_dotprod_route": (i, [i, u, i, ull]),

@@ -65,78 +65,141 @@ ENVELOPES = ["burst", "gaps"]
 # kind: "pfb2" (firpfbch2, q = m) or "pfb" (firpfbch, q = p); an: analyzer;
 # t: "crcf" / "cccf"; S: blocks one workgroup run or set covers on the row's
 # kernel; mode: None, "few" (calls of at most 16 blocks) or "unaligned" (the
-# input at a pointer that is 8 but not 16 bytes aligned, device calls only)
-Row = collections.namedtuple("Row", "kind an t M q S mode")
+# input at a pointer that is 8 but not 16 bytes aligned, device calls only);
+# route: what liquidmi.firpfbch2_route / firpfbch_route must answer for the
+# row's stream in one call (for `few' rows: for a call of 16 blocks).  The
+# query is the launch's own decision, and tests/test_pfb_bound.py holds every
+# row to its route and to run == S, so neither is a comment.
+# nb: the stream's length in blocks where it is not 3S + 4 windows + 5 (the
+# long-run rows of tests/test_gpu_pfb_bound.py, whose S comes from the query).
+Row = collections.namedtuple("Row", "kind an t M q S mode route nb", defaults=(None, None))
 
 
 def _rows(kind, an, t, specs):
-    return [Row(kind, an, t, M, q, S, mode) for M, q, S, mode in specs]
+    return [Row(kind, an, t, M, q, S, mode, route) for M, q, S, mode, route in specs]
 
 
-# firpfbch2 analyzer (M, m, S, mode)
+# firpfbch2 analyzer (M, m, S, mode, route)
 PFB2_AN = _rows("pfb2", True, "crcf", [
-    (2, 1, 512, None),        # k_pfb2_an<2>: 1024 / M blocks per workgroup
-    (8, 2, 128, None),        # k_pfb2_an<8>
-    (12, 3, 1, None),         # k_pfb2_an_generic (direct DFT): one block per workgroup
-    (4, 1, 256, None),        # k_pfb2_an<4>
-    (64, 9, 16, None),        # k_pfb2_an<64> (2m > 16): 16 blocks per workgroup
-    (1024, 9, 1, None),       # k_pfb2_an<1024>: one block per workgroup
-    (64, 2, 64, None),        # k_pfb2_an_small: runs of 32 rows = 64 blocks per set
-    (128, 4, 64, None),       # k_pfb2_an_small
-    (256, 2, 64, None),       # k_pfb2_an256<L, 1>: runs of 32 rows
-    (512, 3, 64, None),       # k_pfb2_an256<L, 2>
-    (1024, 2, 64, None),      # k_pfb2_an1024 (streaming): 4 groups of 16 blocks
-    (1024, 4, 64, None),      # k_pfb2_an1024
-    (1024, 2, 16, "few"),     # k_pfb2_an1024_few: one workgroup per call of <= 16 blocks
-    (1024, 4, 16, "few"),     # k_pfb2_an1024_few
-    (1024, 4, 64, "unaligned"),   # k_pfb2_an1024<L, false>: the unpaired 8-byte loads
-    (1024, 3, 48, None),      # k_pfb2_poly<6>: runs of 4L = 24 rows
-    (256, 8, 128, None),      # k_pfb2_poly<16>: 64 rows
-    (8192, 2, 32, None),      # k_pfb2_poly<4>: 16 rows
-    (2048, 2, 64, None),      # k_pfb2_an2048: runs of 32 rows
-    (4096, 2, 64, None),      # k_pfb2_an4096: runs of 32 rows
+    (2, 1, 512, None, "pfb2_direct"),         # k_pfb2_an<2>: 1024 / M blocks per workgroup
+    (8, 2, 128, None, "pfb2_direct"),         # k_pfb2_an<8>
+    (12, 3, 1, None, "pfb2_generic"),         # k_pfb2_an_generic (direct DFT): one block per workgroup
+    (4, 1, 256, None, "pfb2_direct"),         # k_pfb2_an<4>
+    (64, 9, 16, None, "pfb2_direct"),         # k_pfb2_an<64> (2m > 16): 16 blocks per workgroup
+    (1024, 9, 1, None, "pfb2_direct"),        # k_pfb2_an<1024>: one block per workgroup
+    (64, 2, 64, None, "pfb2_an_small"),       # k_pfb2_an_small: runs of 32 rows = 64 blocks per set
+    (128, 4, 64, None, "pfb2_an_small"),      # k_pfb2_an_small
+    (256, 2, 64, None, "pfb2_an256"),         # k_pfb2_an256<L, 1>: runs of 32 rows
+    (512, 3, 64, None, "pfb2_an512"),         # k_pfb2_an256<L, 2>
+    (1024, 2, 64, None, "pfb2_an1024"),       # k_pfb2_an1024 (streaming): 4 groups of 16 blocks
+    (1024, 4, 64, None, "pfb2_an1024"),       # k_pfb2_an1024
+    (1024, 2, 16, "few", "pfb2_an1024_few"),  # k_pfb2_an1024_few: one workgroup per call of <= 16 blocks
+    (1024, 4, 16, "few", "pfb2_an1024_few"),  # k_pfb2_an1024_few
+    (1024, 4, 64, "unaligned", "pfb2_an1024_unpaired"),   # k_pfb2_an1024<L, false>: the unpaired 8-byte loads
+    (1024, 3, 48, None, "pfb2_poly+fft"),     # k_pfb2_poly<6>: runs of 4L = 24 rows
+    (256, 8, 128, None, "pfb2_poly+fft"),     # k_pfb2_poly<16>: 64 rows
+    (8192, 2, 32, None, "pfb2_poly+fft"),     # k_pfb2_poly<4>: 16 rows
+    (2048, 2, 64, None, "pfb2_an2048"),       # k_pfb2_an2048: runs of 32 rows
+    (4096, 2, 64, None, "pfb2_an4096"),       # k_pfb2_an4096: runs of 32 rows
+    (16, 2, 64, None, "pfb2_direct"),         # k_pfb2_an<16>: 64 blocks per workgroup
 ])
-# firpfbch2 synthesizer (M, m, S, mode)
+# firpfbch2 synthesizer (M, m, S, mode, route)
 PFB2_SYN = _rows("pfb2", False, "crcf", [
-    (12, 3, 64, None),        # batched transform + k_pfb2_syn_out_run<6>: a lane runs 64 blocks
-    (64, 4, 64, None),        # batched transform + k_pfb2_syn_out_run<8>
-    (256, 2, 64, None),       # k_pfb2_syn_fused<4, 1>: runs of 64 blocks
-    (512, 4, 64, None),       # k_pfb2_syn_fused<8, 2>
-    (1024, 2, 32, None),      # k_pfb2_syn1024<4>: 2 groups of 16 blocks
-    (1024, 4, 32, None),      # k_pfb2_syn1024<8>
-    (4096, 2, 33, None),      # k_pfb2_syn4096<4>: runs of 33 blocks
+    (12, 3, 64, None, "pfb2_two_pass_run"),   # batched transform + k_pfb2_syn_out_run<6>: a lane runs 64 blocks
+    (64, 4, 64, None, "pfb2_two_pass_run"),   # batched transform + k_pfb2_syn_out_run<8>
+    (256, 2, 64, None, "pfb2_syn_fused"),     # k_pfb2_syn_fused<4, 1>: runs of 64 blocks
+    (512, 4, 64, None, "pfb2_syn_fused"),     # k_pfb2_syn_fused<8, 2>
+    (1024, 2, 32, None, "pfb2_syn1024"),      # k_pfb2_syn1024<4>: 2 groups of 16 blocks
+    (1024, 4, 32, None, "pfb2_syn1024"),      # k_pfb2_syn1024<8>
+    (4096, 2, 33, None, "pfb2_syn4096"),      # k_pfb2_syn4096<4>: runs of 33 blocks
+    (64, 1, 1, None, "pfb2_two_pass_elem"),   # batched transform + k_pfb2_syn_out (2m = 2 has no ring): per element
+    (12, 5, 1, None, "pfb2_two_pass_elem"),   # batched direct DFT + k_pfb2_syn_out (2m = 10)
 ])
-# firpfbch analyzer (M, p, S, mode), crcf
+# firpfbch analyzer (M, p, S, mode, route), crcf
 PFB_AN = _rows("pfb", True, "crcf", [
-    (10, 5, 1, None),         # k_pfb_an_X (per element) + batched direct DFT
-    (64, 8, 32, None),        # k_pfb_an_small: runs of 32 blocks
-    (256, 4, 32, None),       # k_pfb_an_fused
-    (1024, 4, 32, None),      # k_pfb_an1024<4, 16>: 2 groups of 16 blocks
-    (1024, 8, 32, None),      # k_pfb_an1024<8, 8>
-    (4096, 4, 32, None),      # k_pfb_an4096
-    (1024, 4, 16, "few"),     # k_pfb_an1024_few<4>
-    (1024, 8, 16, "few"),     # k_pfb_an1024_few<8>
+    (10, 5, 1, None, "pfb_an_elem+fft"),      # k_pfb_an_X (per element) + batched direct DFT
+    (64, 8, 32, None, "pfb_an_small"),        # k_pfb_an_small: runs of 32 blocks
+    (256, 4, 32, None, "pfb_an_fused"),       # k_pfb_an_fused
+    (1024, 4, 32, None, "pfb_an1024"),        # k_pfb_an1024<4, 16>: 2 groups of 16 blocks
+    (1024, 8, 32, None, "pfb_an1024"),        # k_pfb_an1024<8, 8>
+    (4096, 4, 32, None, "pfb_an4096"),        # k_pfb_an4096
+    (1024, 4, 16, "few", "pfb_an1024_few"),   # k_pfb_an1024_few<4>
+    (1024, 8, 16, "few", "pfb_an1024_few"),   # k_pfb_an1024_few<8>
+    (2048, 4, 64, None, "pfb_an_run+fft"),    # k_pfb_an_X_run<4, float>: a lane runs 64 blocks; batched transform
+    (1024, 4, 32, "unaligned", "pfb_an1024_unpaired"),   # k_pfb_an1024<4, 16, false>: the unpaired 8-byte loads
 ])
-# firpfbch synthesizer (M, p, S, mode), crcf
+# firpfbch synthesizer (M, p, S, mode, route), crcf
 PFB_SYN = _rows("pfb", False, "crcf", [
-    (10, 5, 1, None),         # batched direct DFT + k_pfb_syn_out (per element)
-    (64, 8, 64, None),        # k_pfb_syn_small: runs of 64 blocks
-    (256, 4, 64, None),       # k_pfb_syn_fused
-    (1024, 4, 32, None),      # k_pfb_syn1024<4>: 2 groups of 16 blocks
-    (1024, 8, 32, None),      # k_pfb_syn1024<8>
-    (4096, 4, 33, None),      # k_pfb_syn4096: runs of 33 blocks
-    (1024, 4, 16, "few"),     # k_pfb_syn1024<4> a group at a time; under 3 blocks the two-pass form
-    (1024, 8, 16, "few"),     # k_pfb_syn1024<8>; under 7 blocks batched transform + k_pfb_syn_out_run<8>
+    (10, 5, 1, None, "pfb_fft+syn_elem"),     # batched direct DFT + k_pfb_syn_out (per element)
+    (64, 8, 64, None, "pfb_syn_small"),       # k_pfb_syn_small: runs of 64 blocks
+    (256, 4, 64, None, "pfb_syn_fused"),      # k_pfb_syn_fused
+    (1024, 4, 32, None, "pfb_syn1024"),       # k_pfb_syn1024<4>: 2 groups of 16 blocks
+    (1024, 8, 32, None, "pfb_syn1024"),       # k_pfb_syn1024<8>
+    (4096, 4, 33, None, "pfb_syn4096"),       # k_pfb_syn4096: runs of 33 blocks
+    # calls of 16 blocks are one group in one workgroup (the query's run is the
+    # workgroup's reach, 2 groups): the seams are the calls', S = 16
+    (1024, 4, 16, "few", "pfb_syn1024"),      # k_pfb_syn1024<4>; under 3 blocks the two-pass form
+    (1024, 8, 16, "few", "pfb_syn1024"),      # k_pfb_syn1024<8>; under 7 blocks batched transform + k_pfb_syn_out_run<8>
+    (2048, 4, 64, None, "pfb_fft+syn_run"),   # batched transform + k_pfb_syn_out_run<4, float>: a lane runs 64 blocks
 ])
-# firpfbch with complex taps: the same kernels with float2 coefficients
-PFB_CCCF = (_rows("pfb", True, "cccf", [(64, 4, 32, None), (256, 4, 32, None), (4096, 4, 32, None)])
-            + _rows("pfb", False, "cccf", [(64, 4, 64, None), (256, 4, 64, None), (4096, 4, 33, None)]))
+# firpfbch with complex taps: the same kernels with float2 coefficients; M = 1024
+# has no fast form for them (k_pfb_an_X_run / k_pfb_syn_out_run<4, float2>)
+PFB_CCCF = (_rows("pfb", True, "cccf", [(64, 4, 32, None, "pfb_an_small_c"), (256, 4, 32, None, "pfb_an_fused_c"),
+                                        (4096, 4, 32, None, "pfb_an4096_c")])
+            + _rows("pfb", False, "cccf", [(64, 4, 64, None, "pfb_syn_small_c"), (256, 4, 64, None, "pfb_syn_fused_c"),
+                                           (4096, 4, 33, None, "pfb_syn4096_c")])
+            + _rows("pfb", True, "cccf", [(1024, 4, 64, None, "pfb_an_run+fft_c"), (10, 5, 1, None, "pfb_an_elem+fft_c")])
+            + _rows("pfb", False, "cccf", [(1024, 4, 64, None, "pfb_fft+syn_run_c"),
+                                           (10, 5, 1, None, "pfb_fft+syn_elem_c")]))
 ROWS = PFB2_AN + PFB2_SYN + PFB_AN + PFB_SYN + PFB_CCCF
+
+# Pieces too short for a row's kernel go down the ladder: {route: (pieces of
+# fewer blocks than this, the route they take)}; `_c' routes as their real one.
+SHORT = {
+    "pfb2_syn1024": (lambda r: 4 * r.q - 1, "pfb2_two_pass_run"),     # the state is 4m - 1 transforms
+    "pfb2_syn4096": (lambda r: 4 * r.q - 1, "pfb2_two_pass_run"),
+    "pfb2_syn_fused": (lambda r: 16, "pfb2_two_pass_run"),            # one group of 16 blocks
+    "pfb_syn1024": (lambda r: r.q - 1, "pfb_fft+syn_run"),            # the state is p - 1 transforms
+    "pfb_syn4096": (lambda r: r.q, "pfb_fft+syn_run"),
+    "pfb_syn_fused": (lambda r: r.q, "pfb_fft+syn_run"),
+    "pfb_syn_small": (lambda r: r.q, "pfb_fft+syn_run"),
+}
+COPYOUT_MAX = 64 << 10      # liquid_mi355x_copyout_max(): the host calls' pinned completion buffer
+
+
+def piece_route(r, n, host):
+    """The route a call of n blocks of row r's object takes; host: through
+    execute_block on host pointers.  The M = 1024 analyzers send calls of at
+    most 16 blocks to the few-block kernel, which also raises the completion
+    flag of a host call whose output fits COPYOUT_MAX."""
+    c = "_c" if r.route.endswith("_c") else ""
+    base = r.route[:len(r.route) - len(c)]
+    if base in SHORT:
+        below, other = SHORT[base]
+        return other + c if n < below(r) else r.route
+    for fam in ("pfb2_an1024", "pfb_an1024"):
+        if base.startswith(fam) and n <= 16:
+            return fam + ("_few_signal" if host and n * r.M * 8 <= COPYOUT_MAX else "_few")
+    return r.route
+
+
+def ways(r):
+    """How the GPU tests run a row: (name, cuts in blocks, host pointers)."""
+    few = few_cuts(r) if r.mode == "few" else []
+    if r.mode == "unaligned":
+        return [("device", few, False), ("device-ragged", cuts(r), False)]
+    return [("one-call", few, True), ("ragged", cuts(r), True), ("device", few, False)]
+
+
+def pieces(r, at):
+    """(first block, blocks) of each call for cuts `at'."""
+    e = [0] + list(at) + [n_blocks(r)]
+    return list(zip(e[:-1], np.diff(e).tolist()))
 
 
 def row_id(r):
-    return "%s-%s-%s-M%d-%s%d%s" % (r.kind, "an" if r.an else "syn", r.t, r.M, "m" if r.kind == "pfb2" else "p", r.q,
-                                    "-" + r.mode if r.mode else "")
+    return "%s-%s-%s-M%d-%s%d%s%s" % (r.kind, "an" if r.an else "syn", r.t, r.M, "m" if r.kind == "pfb2" else "p", r.q,
+                                      "-" + r.mode if r.mode else "", "-S%d-nb%d" % (r.S, r.nb) if r.nb else "")
 
 
 def window_blocks(r):
@@ -146,7 +209,7 @@ def window_blocks(r):
 
 
 def n_blocks(r):
-    return 3 * r.S + 4 * window_blocks(r) + 5
+    return r.nb or 3 * r.S + 4 * window_blocks(r) + 5
 
 
 def nin(r):
